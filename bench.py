@@ -2,8 +2,12 @@
 """bench.py — pictures/sec of the MI355X hot path on work lists RECORDED from the reference encoder, with the roofline of the dominant kernel, in-run parity, the CPU baseline
 and the end-to-end encoder.  The LAST stdout line is one compact JSON object (<= 8 KB, tools/bench_line.py); the full result goes to bench_detail.json and to stdout before it.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...)
+
+A plain run measures `value` alone: it records (or loads) the lists, warms up, times the K steps and prints the line.  --full adds everything listed under "Objects of the
+result" below (and, for N > 1, the same steps with leg C, without the exchange and the other exchange cadences).  --dump-outputs DIR writes what the last timed step computed
+as DIR/<name>.npy (tools/bench_outputs.py: in an order keyed by the inputs, so two builds can be compared output for output).
 
 `value` (BASELINE configs[1]): a step = ONE picture's hot-path work exactly as the reference encoder produced it.  Before the clock starts the encoder built with the binding
 (bindings/vvenc) encodes the 1920x1080 10-bit config-2 clip (65 frames, preset faster) on its CPU kernels with the work-list recorder on (hook bit 131072): every call through
@@ -18,7 +22,7 @@ per GOP cycle of 32 steps and rank: north_star's sharding by GOPs — every rank
 (DESIGN 7).  Reported next to it for N > 1: no_exchange (kernel scaling alone) and exchange_every_reference (a broadcast every 2 steps: the case in which the pictures of ONE
 GOP are spread over the ranks and all 16 reference pictures of the cycle cross — the worst case, `value`'s cadence up to round 5).
 
-Objects of the result (rank 0; each can be switched off; a failure is reported in place and never costs the headline).  In the compact line: a summary of each.
+Objects of the result with --full (rank 0; each can be switched off; a failure is reported in place and never costs the headline).  In the compact line: a summary of each.
   roofline      dominant kernel: achieved = algorithmic bytes (SURVEY 8d per batch unit) / launch time from this run's rocprofv3 kernel trace, frac = achieved / 8 TB/s; traffic =
                 fabric bytes per launch from this run's --pmc passes (calibrated on this GPU); frac_physical, frac_unique; the L1 / VALU fractions and which resource binds;
                 cross-checks (no class above peak, the step's sum below peak) decide whether `basis` may call it an HBM fraction (tools/bench_profile.py)
@@ -54,6 +58,7 @@ from vvenc_amd import sharding  # noqa: E402
 from bench_common import GOP_WEIGHT, KERNEL_NAMES, LAYER_POCS, STEP_LAYERS, kernel_label, layer_of_step, prepare_recordings, step_of_rank  # noqa: E402,F401
 from bench_reference import ReferenceJobs, RecJob, cpu_baseline, parity_check  # noqa: E402,F401  (tests import these through bench)
 import bench_line  # noqa: E402
+import bench_outputs  # noqa: E402
 import bench_mctf as BM  # noqa: E402
 
 
@@ -68,7 +73,7 @@ def replay_pass(args, hp, rank, world, width, height, steps, warmup):
     sharding.barrier()
     if rank != 0:
         pics, _ = prepare_recordings(width, height, 65, sorted(LAYER_POCS.values()))
-    workloads = {layer: RecordedWorkload(hp, pics[poc]) for layer, poc in LAYER_POCS.items()}
+    workloads = {layer: RecordedWorkload(hp, pics[poc], unique_bytes=args.full) for layer, poc in LAYER_POCS.items()}          # (unique bytes: --full's roofline)
     for l, wl in workloads.items():
         if not wl.nothing_dropped:
             raise RuntimeError("layer %d: recorded calls outside the lists: %s" % (l, wl.dropped))
@@ -85,7 +90,7 @@ def replay_pass(args, hp, rank, world, width, height, steps, warmup):
 
     # ---- north-star leg C at the GOP's cadence (tools/bench_mctf.py): the cycle's four filtered pictures resident, issued on two more streams (the cycle's four jobs in turn) by the steps that replay them
     mc = None
-    if not args.no_mctf and (world == 1 or (width, height) == (args.width, args.height)):
+    if args.full and not args.no_mctf and (world == 1 or (width, height) == (args.width, args.height)):
         n_ml = max(1, int(os.environ.get("VVHIP_BENCH_MCTF_LANES", "2"))) if (args.streams > 1 and world == 1) else 1
         mk = lambda: hp.fork(None if os.environ.get("VVHIP_BENCH_TORCH_STREAMS") != "1" else torch.cuda.Stream())
         mc = BM.MctfCadence(hp, width, height, lane=mk() if args.streams > 1 else hp, more_lanes=[mk() for _ in range(n_ml - 1)])
@@ -184,6 +189,51 @@ def replay_pass(args, hp, rank, world, width, height, steps, warmup):
     enq_us = sorted(1e6 * (b - a) for a, b in zip(enq[:-1], enq[1:]))
     dt = sharding.max_over_ranks(dt_local, device="cuda")
     ex_count_timed = ex_count[0] - ex_before
+
+    def headline():
+        """`value` and the description of the workload (rank 0)"""
+        for wl in workloads.values():
+            wl.update_tu_alg_bytes()                     # (sparse-output contract: 2 w h + 24 for a TU whose levels are all zero — from the statistics of the runs so far)
+        frames = steps * world
+        pairs_by_layer = {l: workloads[l].pic.sample_pairs for l in workloads}
+        wsum = float(sum(GOP_WEIGHT.values()))
+        lay_seq = [layer_of_step(step_of_rank(i, rank, world)) for i in range(steps)]
+        out = {
+            "value": frames / dt, "unit": "frames/s", "steps": steps, "warmup": warmup, "ms_per_step": 1000.0 * dt / steps,
+            "host_enqueue_us_per_step": {"p50": round(enq_us[len(enq_us) // 2], 1), "p90": round(enq_us[int(len(enq_us) * 0.9)], 1), "max": round(enq_us[-1], 1),
+                                         "drain_ms_after_last_enqueue": round(1000.0 * (t0 + dt_local - enq[-1]), 3)},
+            "config": {"workload": "%shot-path work lists RECORDED from the reference encoder (%dx%d 10-bit synthetic clip, 65 frames, preset faster; one picture per temporal layer), "
+                                   "replayed resident in HBM: a step = one picture's integer-ME SAD windows + sub-pel SATD stages + table calls + fused TU transform/quant lists + DMVR lists on 5 HIP streams; "
+                                   "steps follow the GOP's 1:1:2:4:8:16 layer mix from the key picture on" % ("BASELINE configs[1]: " if ( width, height ) == ( 1920, 1080 ) else ( "BASELINE configs[2]'s geometry: " if ( width, height ) == ( 3840, 2160 ) else "(test size) " ), width, height),
+                       "layer_pocs": {str(l): p for l, p in LAYER_POCS.items()},
+                       "pictures_per_32_steps_by_layer": {str(l): GOP_WEIGHT[l] for l in GOP_WEIGHT},
+                       "pictures_in_the_timed_steps_by_layer": {str(l): lay_seq.count(l) for l in range(6)},
+                       "sample_pairs_per_frame": int(sum(GOP_WEIGHT[l] * pairs_by_layer[l] for l in pairs_by_layer) / wsum),
+                       "sample_pairs_per_frame_by_layer": {str(l): int(v) for l, v in pairs_by_layer.items()},
+                       "sample_pairs_note": "counted like the reference's own counter (CommonLib/SearchSpaceCounter.cpp:106-165 via RdCost.cpp:150-156: w x h per table call, DMVR excluded): "
+                                            "%.1f x 1.5 W H GOP-weighted" % (sum(GOP_WEIGHT[l] * pairs_by_layer[l] for l in pairs_by_layer) / wsum / (1.5 * width * height)),
+                       "coefficients_per_frame": int(sum(GOP_WEIGHT[l] * workloads[l].tu_coefficients for l in workloads) / wsum),
+                       "work_per_layer": {str(l): {"me_calls": int(workloads[l].pic.me.size), "integer_candidates": int(workloads[l].plan_cands.size), "integer_positions_distinct": workloads[l].distinct_positions,
+                                                   "subpel_stages": int(workloads[l].stage_jobs.size), "subpel_positions": int(workloads[l].stage_evaluated.sum()), "table_calls": int(workloads[l].items.size), "tus": int(sum(g["n"] for g in workloads[l].tu_groups)),
+                                                   "dmvr_subblocks": int(sum(g["n"] for g in workloads[l].dmvr_groups)), "plan": workloads[l].me_info} for l in workloads},
+                       "recorded_calls_outside_the_lists": 0,
+                       "tu_outputs": ("sparse (vvhip_tu_set_sparse_outputs): a TU whose levels are all zero gets its statistics only, as the reference's caller reads neither its levels nor its "
+                                      "reconstruction (InterSearch.cpp:3696-3714); all-zero TUs by layer: %s" % {str(l): workloads[l].tu_zero_share for l in workloads})
+                                     if all(getattr(workloads[l], "tu_sparse", False) for l in workloads) else "dense: every output of every TU is written",
+                       "subpel_candidates_per_block": round(float(np.mean([workloads[l].stage_evaluated.sum() / max(1, workloads[l].pic.me.size) for l in workloads if workloads[l].pic.me.size])), 2),
+                       "launches_per_frame": "motion-search plan (refinement stages per tap set + integer windows + table calls) + 1 TU launch (+ one per rectangular TU shape) + 0-1 DMVR launch per reference pair",
+                       "schedule": "workgroups of every launch in XCD-band order: XCD x (workgroup index mod 8) takes the x-th contiguous eighth of each class in picture order ($VVHIP_ME_XCD_BAND=0: heaviest first)",
+                       "hip_streams": len(lanes) if lanes else 1, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), "recording": rec_info,
+                       "sharding": "one picture per rank and step: rank r replays position k + 32 r / N of the cycle at its step k (N different pictures of one sequence at any time, the same layer mix per rank), no data-path collective"
+                                   + (", reconstructed picture (luma + chroma, %.1f MB) RCCL-broadcast from its owner every %d step(s) inside the timed region, overlapped with the launches"
+                                      % (sum(p.numel() * 2 for p in ex.slots[0]) / 1e6, args.exchange_every) if ex is not None else "")},
+        }
+        return out
+
+    if args.dump_outputs and rank == 0:
+        bench_outputs.dump(workloads[layer_of_step(step_of_rank(steps - 1, rank, world))], args.dump_outputs)
+    if not args.full:
+        return (headline() if rank == 0 else None), workloads, None
 
     # ---- the same K steps WITH leg C: the steps that replay the POC-32 / 16 / 8 / 24 pictures also queue that picture's MCTF (4 / 4 / 2 / 2 motion estimations + the filter
     #      of Y, U, V) on the MCTF lanes — `value_with_mctf`; and whole GOP cycles (the cadence's stable figure: 12 estimations + 4 filters per 32 steps)
@@ -356,42 +406,8 @@ def replay_pass(args, hp, rank, world, width, height, steps, warmup):
     if rank != 0:
         return None, workloads, None
 
-    for wl in workloads.values():
-        wl.update_tu_alg_bytes()                         # (sparse-output contract: 2 w h + 24 for a TU whose levels are all zero — from the statistics of the runs above)
-    frames = steps * world
-    pairs_by_layer = {l: workloads[l].pic.sample_pairs for l in workloads}
+    out = headline()
     wsum = float(sum(GOP_WEIGHT.values()))
-    lay_seq = [layer_of_step(step_of_rank(i, rank, world)) for i in range(steps)]
-    out = {
-        "value": frames / dt, "unit": "frames/s", "steps": steps, "warmup": warmup, "ms_per_step": 1000.0 * dt / steps,
-        "host_enqueue_us_per_step": {"p50": round(enq_us[len(enq_us) // 2], 1), "p90": round(enq_us[int(len(enq_us) * 0.9)], 1), "max": round(enq_us[-1], 1),
-                                     "drain_ms_after_last_enqueue": round(1000.0 * (t0 + dt_local - enq[-1]), 3)},
-        "config": {"workload": "%shot-path work lists RECORDED from the reference encoder (%dx%d 10-bit synthetic clip, 65 frames, preset faster; one picture per temporal layer), "
-                               "replayed resident in HBM: a step = one picture's integer-ME SAD windows + sub-pel SATD stages + table calls + fused TU transform/quant lists + DMVR lists on 5 HIP streams; "
-                               "steps follow the GOP's 1:1:2:4:8:16 layer mix from the key picture on" % ("BASELINE configs[1]: " if ( width, height ) == ( 1920, 1080 ) else ( "BASELINE configs[2]'s geometry: " if ( width, height ) == ( 3840, 2160 ) else "(test size) " ), width, height),
-                   "layer_pocs": {str(l): p for l, p in LAYER_POCS.items()},
-                   "pictures_per_32_steps_by_layer": {str(l): GOP_WEIGHT[l] for l in GOP_WEIGHT},
-                   "pictures_in_the_timed_steps_by_layer": {str(l): lay_seq.count(l) for l in range(6)},
-                   "sample_pairs_per_frame": int(sum(GOP_WEIGHT[l] * pairs_by_layer[l] for l in pairs_by_layer) / wsum),
-                   "sample_pairs_per_frame_by_layer": {str(l): int(v) for l, v in pairs_by_layer.items()},
-                   "sample_pairs_note": "counted like the reference's own counter (CommonLib/SearchSpaceCounter.cpp:106-165 via RdCost.cpp:150-156: w x h per table call, DMVR excluded): "
-                                        "%.1f x 1.5 W H GOP-weighted" % (sum(GOP_WEIGHT[l] * pairs_by_layer[l] for l in pairs_by_layer) / wsum / (1.5 * width * height)),
-                   "coefficients_per_frame": int(sum(GOP_WEIGHT[l] * workloads[l].tu_coefficients for l in workloads) / wsum),
-                   "work_per_layer": {str(l): {"me_calls": int(workloads[l].pic.me.size), "integer_candidates": int(workloads[l].plan_cands.size), "integer_positions_distinct": workloads[l].distinct_positions,
-                                               "subpel_stages": int(workloads[l].stage_jobs.size), "subpel_positions": int(workloads[l].stage_evaluated.sum()), "table_calls": int(workloads[l].items.size), "tus": int(sum(g["n"] for g in workloads[l].tu_groups)),
-                                               "dmvr_subblocks": int(sum(g["n"] for g in workloads[l].dmvr_groups)), "plan": workloads[l].me_info} for l in workloads},
-                   "recorded_calls_outside_the_lists": 0,
-                   "tu_outputs": ("sparse (vvhip_tu_set_sparse_outputs): a TU whose levels are all zero gets its statistics only, as the reference's caller reads neither its levels nor its "
-                                  "reconstruction (InterSearch.cpp:3696-3714); all-zero TUs by layer: %s" % {str(l): workloads[l].tu_zero_share for l in workloads})
-                                 if all(getattr(workloads[l], "tu_sparse", False) for l in workloads) else "dense: every output of every TU is written",
-                   "subpel_candidates_per_block": round(float(np.mean([workloads[l].stage_evaluated.sum() / max(1, workloads[l].pic.me.size) for l in workloads if workloads[l].pic.me.size])), 2),
-                   "launches_per_frame": "motion-search plan (refinement stages per tap set + integer windows + table calls) + 1 TU launch (+ one per rectangular TU shape) + 0-1 DMVR launch per reference pair",
-                   "schedule": "workgroups of every launch in XCD-band order: XCD x (workgroup index mod 8) takes the x-th contiguous eighth of each class in picture order ($VVHIP_ME_XCD_BAND=0: heaviest first)",
-                   "hip_streams": len(lanes) if lanes else 1, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), "recording": rec_info,
-                   "sharding": "one picture per rank and step: rank r replays position k + 32 r / N of the cycle at its step k (N different pictures of one sequence at any time, the same layer mix per rank), no data-path collective"
-                               + (", reconstructed picture (luma + chroma, %.1f MB) RCCL-broadcast from its owner every %d step(s) inside the timed region, overlapped with the launches"
-                                  % (sum(p.numel() * 2 for p in ex.slots[0]) / 1e6, args.exchange_every) if ex is not None else "")},
-    }
     if layer_ms:
         ms = sum(GOP_WEIGHT[l] * layer_ms[l] for l in layer_ms) / wsum
         out["gop_weighted"] = {"value": 1000.0 / ms, "unit": "frames/s", "ms_per_picture_by_layer": {str(l): round(v, 4) for l, v in layer_ms.items()},
@@ -450,7 +466,7 @@ def replay_pass(args, hp, rank, world, width, height, steps, warmup):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=64, help="timed steps (a step = one picture)")
     ap.add_argument("--warmup", type=int, default=32)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -459,6 +475,9 @@ def main():
     ap.add_argument("--exchange-every", type=int, default=32, help="N > 1: one reference-picture broadcast every this many steps (a step is one picture).  Default 32: every rank works "
                     "on its own GOP chunk and the chunk's key picture is the one reference that crosses ranks; 2 = the pictures of one GOP spread over the ranks (16 of the 32 pictures "
                     "of a random-access GOP cycle, temporal layers 0-4, are references of other pictures) — reported as exchange_every_reference either way")
+    ap.add_argument("--full", action="store_true", help="everything besides `value`: leg C, single-stream / per-layer / per-kernel times, roofline, parity, CPU baseline, 4K, "
+                    "preset medium, the MCTF stage, the end-to-end encoder (the --no-* switches below leave single parts out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB; tools/bench_outputs.py)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-mctf", action="store_true")
@@ -475,6 +494,8 @@ def main():
     ap.add_argument("--inner-mctf", action="store_true", help="(internal) the short run rocprofv3 wraps for the MCTF stage: six motion estimations of one 1080p picture against 4 references")
     ap.add_argument("--inner", action="store_true", help="(internal) the short run rocprofv3 wraps: the recorded pictures' launches serialized on one stream, no extras, no output line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.quick:
         args.no_e2e = args.no_profile = args.no_4k = args.no_mctf = args.no_cpu_baseline = args.no_medium = True
 
@@ -511,7 +532,7 @@ def main():
 
     core, workloads, kern = replay_pass(args, hp, rank, world, args.width, args.height, args.steps, args.warmup)
     inst = None
-    if world > 1 and not args.no_e2e:
+    if world > 1 and args.full and not args.no_e2e:
         try:
             inst = BE.e2e_instances(rank, local_rank, world)
         except Exception as e:
@@ -527,6 +548,9 @@ def main():
         out["value_with_mctf"], out["ms_per_step_with_mctf"] = core["with_mctf"]["value"], core["with_mctf"]["ms_per_step"]
     if inst is not None:
         out["e2e_instances"] = inst
+    if not args.full:
+        bench_line.emit(out, ROOT, args.detail)
+        return
     can_profile = not args.no_profile and world == 1 and bool(shutil.which("rocprofv3"))
 
     def profiled(width, height, kern_, workloads_, ms_per_step, md, mc_=None):

@@ -1,5 +1,5 @@
 """helpers for the end-to-end bitstream tests: drive the reference encoder through its C API — the plain build (oracle/_ref/libvvenc_ref.so, the CPU oracle) and
-the build WITH the MI355X binding (bindings/vvenc/_build/libvvenc_hip_enc.so, product; bindings/vvenc/Makefile)"""
+the build WITH the MI355X binding (oracle/_ref/libvvenc_hip_enc.so, product; bindings/vvenc/Makefile)"""
 import ctypes as C
 import hashlib
 import os
@@ -8,7 +8,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libvvenc_ref.so")
-REF_HIP_SO = os.path.join(ROOT, "bindings", "vvenc", "_build", "libvvenc_hip_enc.so")
+REF_HIP_SO = os.path.join(ROOT, "oracle", "_ref", "libvvenc_hip_enc.so")
 PRESET_FASTER, PRESET_FAST, PRESET_MEDIUM = 0, 1, 2   # vvencPresetMode (include/vvenc/vvencCfg.h)
 PRESETS = {"faster": 0, "fast": 1, "medium": 2}
 

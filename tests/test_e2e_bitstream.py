@@ -68,7 +68,7 @@ def test_reference_rows_agree(clip):
 @pytest.mark.parametrize("clip", [CFG1, CFG10], ids=["cfg0-64x64-8b", "128x64-10b"])
 def test_hip_backend_bitstream_identical(clip):
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     cpu = run(dict(clip, hip=False, simd=None, mask=0))
     hip = run(dict(clip, hip=True, simd=None, mask=31))
     print("cpu", cpu, "hip", hip)
@@ -81,7 +81,7 @@ def test_hip_table_entries_only_bitstream_identical():
     """same gate with the MCTF search left to the reference's own schedule calling our per-candidate table entries
     (m_motionErrorLumaInt8 / m_motionErrorLumaFrac8[1] / m_calcVar through the shim) instead of the whole-picture device ME"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     cpu = run(dict(CFG1, hip=False, simd=None, mask=0))
     hip = run(dict(CFG1, hip=True, simd=None, mask=15))
     print("cpu", cpu, "hip", hip)
@@ -94,7 +94,7 @@ def test_hip_tcoeffops_slots_bitstream_identical():
     """the reference's global g_tCoeffOps pointed at the device slots (identical signatures, zero source change): every matrix-core
     pass, round/clip and Pel<->TCoeff copy of the encode runs on the GPU one call at a time; bitstream must not change"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     cpu = run(dict(CFG1, hip=False, simd=None, mask=0))
     hip = run(dict(CFG1, hip=True, simd=None, mask=32))
     print("cpu", cpu, "hip", hip)
@@ -108,7 +108,7 @@ def test_hip_interpolation_tables_bitstream_identical():
     the device entries, so all motion compensation and sub-pel refinement planes of the encode are interpolated on the GPU (one call at a
     time); bitstream must not change"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     cpu = run(dict(CFG1, hip=False, simd=None, mask=0))
     hip = run(dict(CFG1, hip=True, simd=None, mask=64))
     print("cpu", cpu, "hip", hip)
@@ -123,7 +123,7 @@ def test_hip_mctf_stage_on_device_bitstream_identical(clip):
     (mask 128) — against the CPU encode.  The device filter equals the reference's scalar row; its AVX2 row (the CPU run here) is allowed
     +-1 by the reference's unit test, and on these clips the bitstreams are identical."""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     cpu = run(dict(clip, hip=False, simd=None, mask=0))
     hip = run(dict(clip, hip=True, simd=None, mask=16 + 128))
     print("cpu", cpu, "hip", hip)
@@ -137,7 +137,7 @@ def test_hip_backend_multithreaded_encoder_bitstream_identical():
     are shared: SURVEY 8b "Threading"); the shim serialises its staging area.  Every table on the device (mask 31 + interpolation 64 +
     MCTF filter 128), bitstream equal to the single-threaded CPU encode's (the reference's multi-threading is deterministic)."""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     cpu = run(dict(CFG10, hip=False, simd=None, mask=0, threads=4))
     hip = run(dict(CFG10, hip=True, simd=None, mask=31 + 64 + 128, threads=4))
     print("cpu", cpu, "hip", hip)
@@ -152,7 +152,7 @@ def test_hip_batched_subpel_refinement_bitstream_identical(clip):
     (up to) nine candidate costs from ONE vvhip_subpel_refine_batch call (through vvhip::RdCost::patternRefineCosts); the encoder's own loop
     replays them (skip and break rules, MV-bit costs, strict < update, patternId bookkeeping).  Everything else on the CPU."""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     cpu = run(dict(clip, hip=False, simd=None, mask=0))
     hip = run(dict(clip, hip=True, simd=None, mask=256))
     print("cpu", cpu, "hip", hip)
@@ -167,7 +167,7 @@ def test_hip_dmvr_search_bitstream_identical(clip):
     vvhip_dmvr_refine_batch call (vvhip::DMVROps::refineCu); the encoder copies mvdL0SubPu / the BDOF switch from the results and does the final
     motion compensation itself.  DMVR is decoder-normative: any deviation changes the bitstream."""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     cpu = run(dict(clip, hip=False, simd=None, mask=0))
     hip = run(dict(clip, hip=True, simd=None, mask=512))
     print("cpu", cpu, "hip", hip)
@@ -181,7 +181,7 @@ def test_hip_alf_statistics_bitstream_identical():
     device (hook mask 2048, vvhip::ALFOps) instead of deriveClassification / getPreBlkStats.  The ALF filter derivation works on these floats — a single
     differently rounded sum can change a coefficient — so identical bitstreams pin the float accumulation order in the real pipeline."""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=208, h=120, frames=9, in_bd=10, int_bd=10, threads=2)
     cpu = run(dict(clip, hip=False, simd=None, mask=0))
     hip = run(dict(clip, hip=True, simd=None, mask=2048 + 4096))
@@ -195,7 +195,7 @@ def test_hip_alf_picture_statistics_bitstream_identical():
     """the whole-picture form (hook mask 8192): the per-CTU statistics tasks of the encoder do nothing, EncAdaptiveLoopFilter::deriveFilter starts with ONE device
     call per picture (classification + luma / chroma records of every 128x128 statistics unit, CTU-by-CTU chains inside a unit); small clip and 1080p"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=208, h=120, frames=9, in_bd=10, int_bd=10, threads=2)
     cpu = run(dict(clip, hip=False, simd=None, mask=0))
     hip = run(dict(clip, hip=True, simd=None, mask=8192))
@@ -214,7 +214,7 @@ def test_hip_alf_statistics_1080p_bitstream_identical():
     """the same at 1080p (preset faster: 64x64 CTUs inside 128x128 statistics units, so the float chains continue from CTU to CTU through the
     start records): 510 CTUs per ALF picture, 8 encoder threads"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     import e2e_fps
     res = [e2e_fps.run(dict(w=1920, h=1080, frames=9, threads=8, mask=m)) for m in (0, 2048 + 4096)]
     print(res)
@@ -228,7 +228,7 @@ def test_hip_alf_filtering_bitstream_identical():
     and applyCcAlfFilterCTU hands to m_filterCcAlf is filtered on the device instead.  The filtered reconstruction is the reference of the following pictures, so one
     differing sample changes the bitstream.  Small clip, and 1080p with the statistics on the device as well (8 encoder threads)."""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=208, h=120, frames=9, in_bd=10, int_bd=10, threads=2)
     cpu = run(dict(clip, hip=False, simd=None, mask=0))
     hip = run(dict(clip, hip=True, simd=None, mask=16384 + 32768))
@@ -247,7 +247,7 @@ def test_hip_alf_picture_filtering_bitstream_identical():
     """the whole ALF stage of a picture in two shim calls (hook masks 8192 + 65536): statistics of every unit before the derivation, and after it the filtering of every
     enabled CTU of the three planes by the first reconstruction task of the picture (the other tasks find the picture done); CC-ALF per block (32768)"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=208, h=120, frames=9, in_bd=10, int_bd=10, threads=2)
     cpu = run(dict(clip, hip=False, simd=None, mask=0))
     hip = run(dict(clip, hip=True, simd=None, mask=8192 + 65536))
@@ -266,7 +266,7 @@ def test_hip_4k_picture_level_stages_bitstream_identical():
     """BASELINE's 4K geometry (3840x2160 10-bit, preset faster) in the real encoder: the picture-level stages on the device — MCTF search + bilateral filter (144), ALF
     statistics (8192) and ALF filtering (65536) of whole pictures — 9 frames, 8 encoder threads"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     import e2e_fps
     res = [e2e_fps.run(dict(w=3840, h=2160, frames=9, threads=8, mask=m)) for m in (0, 144 + 8192 + 65536)]
     print(res)
@@ -279,7 +279,7 @@ def test_hip_everything_on_device_bitstream_identical():
     """all hooks at once on a larger clip (208x120 10-bit, 9 frames, 2 encoder threads): every kernel table, the interpolation tables, whole-picture
     MCTF ME + filter, batched integer diamond rounds, batched sub-pel refinement stages, per-CU DMVR searches, per-CTU ALF statistics and ALF / CC-ALF filtering"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=208, h=120, frames=9, in_bd=10, int_bd=10, threads=2)
     cpu = run(dict(clip, hip=False, simd=None, mask=0))
     hip = run(dict(clip, hip=True, simd=None, mask=31 + 64 + 128 + 256 + 512 + 1024 + 2048 + 4096 + 16384 + 32768))
@@ -295,7 +295,7 @@ def test_hip_batched_tz_diamond_rounds_bitstream_identical(clip):
     may test are scored by ONE device call (vvhip::RdCost::distAtPositions -> vvhip_dist_batch); xTZSearchHelp takes its SAD from that table and
     runs its own update logic (MV-bit cost, strict <).  Everything else on the CPU."""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     cpu = run(dict(clip, hip=False, simd=None, mask=0))
     hip = run(dict(clip, hip=True, simd=None, mask=1024))
     print("cpu", cpu, "hip", hip)
@@ -317,7 +317,7 @@ PICTURE_STAGES = 16 + 128 + 8192 + 65536
 @pytest.mark.parametrize("preset", ["faster", "fast", "medium"])
 def test_hip_presets_all_tables_bitstream_identical(preset):
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(CLIP416, frames=5, preset=preset)
     cpu = run(dict(clip, hip=False, mask=0))
     hip = run(dict(clip, hip=True, mask=ALL_TABLES))
@@ -330,7 +330,7 @@ def test_hip_presets_all_tables_bitstream_identical(preset):
 @pytest.mark.parametrize("preset", ["faster", "fast", "medium"])
 def test_hip_presets_batched_search_sites_bitstream_identical(preset):
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(CLIP416, frames=5, preset=preset)
     cpu = run(dict(clip, hip=False, mask=0))
     hip = run(dict(clip, hip=True, mask=BATCHED_SITES))
@@ -346,7 +346,7 @@ def test_hip_presets_picture_stages_through_simd_switch_bitstream_identical(pres
     """the production selection, --SIMD=HIP (vvenc_set_SIMD_extension("HIP") -> VVEncImpl::setSIMDExtension -> vvenc_hip_select): MCTF search + filter and ALF statistics of
     whole pictures on the device (whole-picture ALF filtering is an explicit mask: it loses at 8 encoder threads); 17 frames so that MCTF filters two pictures"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(CLIP416, frames=17, preset=preset)
     cpu = run(dict(clip, hip=False, mask=0))
     hip = run(dict(clip, hip=True, simd="HIP"))
@@ -363,7 +363,7 @@ def test_hip_cu_level_sites_bitstream_identical(site, first, second):
     """the two CU-level call sites of SURVEY 8a outside the motion search: InterSearch::xEstimateInterResidualQT (a CU's component TUs forward-transformed in one device round
     trip, hook bit 262144) and EncCu::addRegularCandsToPruningList (a CU's regular merge candidates scored in one device call, bit 524288), on the 'pan' clip, 4 threads"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=416, h=240, frames=9, in_bd=10, int_bd=10, clip="pan", threads=4)
     cpu = run(dict(clip, hip=False, simd=None, mask=0))
     hip = run(dict(clip, hip=True, simd=None, mask=site))
@@ -380,7 +380,7 @@ def test_production_mask_equals_the_x86_row_where_the_references_rows_differ():
     silently).  What the row difference is NOT (round 6, CPU tier): the MCTF search and filter — with both replaced by scalar-row arithmetic the encoder still emits the AVX2
     stream (tests/test_binding_sim.py::test_mctf_stages_keep_the_default_stream_on_the_pan_clip), and the filter's two rows agree sample for sample (tolerance 0)."""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=416, h=240, frames=9, in_bd=10, int_bd=10, clip="pan", threads=4)
     default = run(dict(clip, hip=False, simd=None, mask=0))
     scalar = run(dict(clip, hip=False, simd="SCALAR", mask=0))
@@ -404,7 +404,7 @@ def test_hip_lfnst_quantiser_guard_bitstream_identical():
     first-coefficient-group rule (Quant.cpp:149-159).  Round 6: the rule is on the device (vvhip_quant_core_lfnst) — no TU is left to the CPU entry any more (counter 20 == 0,
     counter 38 counts the LFNST TUs the device quantised); $VVHIP_LFNST_QUANT_ON_CPU=1 is the old route and gives the same stream"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=208, h=120, frames=5, in_bd=10, int_bd=10, preset="fast", options="RDOQ=0;DepQuant=0;LFNST=1")
     cpu = run(dict(clip, hip=False, mask=0))
     hip = run(dict(clip, hip=True, mask=4))
@@ -419,7 +419,7 @@ def test_hip_lfnst_quantiser_guard_bitstream_identical():
 def test_hip_4k_medium_picture_stages_bitstream_identical():
     """BASELINE configs[3] geometry: 3840x2160 10-bit, preset medium (CTU 128, MTT), picture-level stages on the device through --SIMD=HIP, 9 frames, 8 threads"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=3840, h=2160, frames=9, in_bd=10, int_bd=10, threads=8, preset="medium", clip="pan")
     cpu = run(dict(clip, hip=False, mask=0))
     hip = run(dict(clip, hip=True, simd="HIP:73872"))          # production set + whole-picture ALF filtering (65536)
@@ -434,7 +434,7 @@ def test_hip_8k_fast_picture_stages_bitstream_identical():
     the encoder — calls[9]: MCTF filter pictures, [21]: device motion-estimation calls, [16] / [19]: ALF statistics / filter pictures), 8 threads (the ALF picture stages go
     to the device only while the thread pool is saturated)"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=7680, h=4320, frames=17, in_bd=10, int_bd=10, threads=8, preset="fast", clip="pan")
     cpu = run(dict(clip, hip=False, mask=0))
     hip = run(dict(clip, hip=True, simd="HIP:73872"))
@@ -449,7 +449,7 @@ def test_hip_pictures_shard_over_logical_devices_bitstream_identical():
     pictures over them — per-device registries, thread -> device binding per picture, device-to-device copies (hipMemcpyPeerAsync) of originals another device already holds.
     Preset medium (overlapping MCTF windows => peer copies), 25 frames, 4 threads; bitstream equal to the CPU encode's"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(CLIP416, frames=25, preset="medium")
     cpu = run(dict(clip, hip=False, mask=0))
     hip = run(dict(clip, hip=True, simd="HIP"), env={"VVHIP_LOGICAL_GPUS": "2", "VVHIP_GPUS": "2"})
@@ -465,7 +465,7 @@ def test_config2_4k_65_frames_faster_production_bitstream_identical():
     """BASELINE configs[2]: 3840x2160 10-bit, 65 frames, preset faster, --SIMD=HIP (MCTF block matching + filter and whole-picture ALF statistics on the MI355X), 8 encoder
     threads: the bitstream of the whole sequence equals the CPU encoder's"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     import e2e_fps
     cpu = e2e_fps.run(dict(w=3840, h=2160, frames=65, threads=8, mask=0), timeout=1200)
     hip = e2e_fps.run(dict(w=3840, h=2160, frames=65, threads=8, mask=16 + 128 + 8192), timeout=1200)
@@ -479,7 +479,7 @@ def test_config3_4k_medium_65_frames_two_logical_devices_bitstream_identical():
     """BASELINE configs[3] geometry over two GOPs + 1: 3840x2160 10-bit, 65 frames, preset medium (CTU 128, MTT), pictures sharded over two logical devices (one physical GPU:
     per-device registries, thread -> device binding, device-to-device picture copies), --SIMD=HIP, 8 threads"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=3840, h=2160, frames=65, in_bd=10, int_bd=10, threads=8, preset="medium", clip="pan")
     cpu = run(dict(clip, hip=False, mask=0))
     hip = run(dict(clip, hip=True, simd="HIP"), env={"VVHIP_LOGICAL_GPUS": "2", "VVHIP_GPUS": "2"})
@@ -499,7 +499,7 @@ def test_config3_4k_medium_129_frames_full_length_production_bitstream_identical
     (8 threads: above that the encoder switches its inter-frame line synchronisation on (m_ifpLines > 0) and the binding leaves the whole-picture ALF statistics to the CPU tasks
     by design, bindings/vvenc/apply_binding.py; the 16-thread run of the same clip — md5 equal, 6.69 -> 7.08 fps — is in profiles/r05_long_gates.log)"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=3840, h=2160, frames=129, in_bd=10, int_bd=10, threads=8, preset="medium", clip="pan")
     cpu = run(dict(clip, hip=False, mask=0), timeout=3000)
     hip = run(dict(clip, hip=True, simd="HIP"), env={"VVHIP_LOGICAL_GPUS": "2", "VVHIP_GPUS": "2"}, timeout=3000)
@@ -515,7 +515,7 @@ def test_config4_8k_fast_65_frames_full_length_production_bitstream_identical():
     """BASELINE configs[4] at full length: 7680x4320 10-bit, 65 frames, preset fast, production mask through --SIMD=HIP, 8 encoder threads: md5 == the CPU encoder's; the
     temporal filter's block matching and the ALF statistics ran on the device at 8K (16 threads, md5 equal, 3.44 -> 3.54 fps: profiles/r05_long_gates.log)"""
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) not built")
     clip = dict(w=7680, h=4320, frames=65, in_bd=10, int_bd=10, threads=8, preset="fast", clip="pan")
     cpu = run(dict(clip, hip=False, mask=0), timeout=3000)
     hip = run(dict(clip, hip=True, simd="HIP"), timeout=3000)

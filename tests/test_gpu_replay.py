@@ -139,7 +139,7 @@ def _record(tmp, width, height, frames, pocs, preset="faster"):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import e2e_util
     if not os.path.exists(e2e_util.REF_HIP_SO):
-        pytest.skip("bindings/vvenc/_build/libvvenc_hip_enc.so (the encoder with the binding) is not built")
+        pytest.skip("oracle/_ref/libvvenc_hip_enc.so (the encoder with the binding) is not built")
     R.record(str(tmp), width, height, frames, pocs=pocs, threads=4, preset=preset)
     return R.load_dir(str(tmp))
 

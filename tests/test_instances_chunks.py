@@ -62,7 +62,7 @@ def test_concurrent_instances_reproduce_the_single_instance_bitstream_of_each_ch
 @pytest.mark.sim
 def test_concurrent_instances_with_the_binding_reproduce_the_cpu_bitstream_of_each_chunk():
     if not (os.path.exists(e2e_util.REF_SO) and os.path.exists(e2e_util.REF_HIP_SO) and os.path.exists(SIM)):
-        pytest.skip("needs oracle/_ref, bindings/vvenc/_build and tests/sim (python __graft_entry__.py)")
+        pytest.skip("needs oracle/_ref/libvvenc_ref.so, oracle/_ref/libvvenc_hip_enc.so and tests/sim (python __graft_entry__.py)")
     if os.path.exists("/dev/kfd"):
         pytest.skip("a GPU is present: the test double refuses to stand in for it")
     prod = 16 + 128 + 8192                                                         # --SIMD=HIP's production mask (bench_encoder.e2e_production_mask)

@@ -22,7 +22,7 @@ import e2e_util  # noqa: E402
 
 def need():
     if not (os.path.exists(e2e_util.REF_SO) and os.path.exists(e2e_util.REF_HIP_SO)):
-        pytest.skip("needs oracle/_ref/libvvenc_ref.so and bindings/vvenc/_build/libvvenc_hip_enc.so (built from /root/reference)")
+        pytest.skip("needs oracle/_ref/libvvenc_ref.so and oracle/_ref/libvvenc_hip_enc.so (built from the reference sources)")
 
 
 @pytest.fixture(scope="module")

@@ -31,7 +31,7 @@ def e2e_encoder(width, height, frames, threads, pairs, other_threads=(), scalar=
     import e2e_fps
     import e2e_util
     if not (os.path.exists(e2e_util.REF_SO) and os.path.exists(e2e_util.REF_HIP_SO)):
-        return {"skipped": "the compiled reference encoder (oracle/_ref) and the encoder with the binding (bindings/vvenc/_build) are not both built"}
+        return {"skipped": "the compiled reference encoder (oracle/_ref) and the encoder with the binding (oracle/_ref/libvvenc_hip_enc.so) are not both built"}
     prod = e2e_production_mask()
     base = dict(w=width, h=height, frames=frames)
     med = lambda v: sorted(v)[len(v) // 2]
@@ -137,7 +137,7 @@ def e2e_instances(rank, local_rank, world, width=1920, height=1080, frames=65):
     import e2e_fps
     import e2e_util
     if not (os.path.exists(e2e_util.REF_SO) and os.path.exists(e2e_util.REF_HIP_SO)):
-        return {"skipped": "the compiled reference encoder (oracle/_ref) and the encoder with the binding (bindings/vvenc/_build) are not both built"} if rank == 0 else None
+        return {"skipped": "the compiled reference encoder (oracle/_ref) and the encoder with the binding (oracle/_ref/libvvenc_hip_enc.so) are not both built"} if rank == 0 else None
     threads = max(1, usable_cores(host_cpu_info()) // world)
     ndev = max(1, torch.cuda.device_count())
     env = dict(os.environ)

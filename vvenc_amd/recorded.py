@@ -133,7 +133,7 @@ print(json.dumps({"md5": md5, "bytes": n, "secs": secs}))
 
 
 def record(out_dir, width=1920, height=1080, frames=65, pocs=(15, 23, 5, 2), threads=8, preset="faster", light=False, timeout=1800):
-    """runs the reference encoder built with the binding (bindings/vvenc/_build/libvvenc_hip_enc.so) on the BASELINE config-2 style clip with the recorder hook:
+    """runs the reference encoder built with the binding (libvvenc_hip_enc.so, bindings/vvenc/Makefile) on the BASELINE config-2 style clip with the recorder hook:
     the encoder keeps its CPU kernels (bitstream = the CPU encoder's), the work lists of the pictures `pocs` land in out_dir.  Needs no GPU."""
     import subprocess
     import sys
