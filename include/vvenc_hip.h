@@ -412,6 +412,57 @@ VVHIP_API int  vvhip_me_plan_last_times( vvhip_ctx* ctx, const vvhip_me_plan* pl
 /* what the schedule looks like (for measurements): waves per list and LDS bytes per wave */
 VVHIP_API int  vvhip_me_plan_info( const vvhip_me_plan* plan, int* waves_int, int* waves_stage, int* waves_item, int* lds_bytes );
 
+/* ======================================================================================================================
+ * Inter prediction of a LIST of prediction units: what InterPredInterpolation::xPredInterBlk + xWeightedAverage produce for one component block of one PU
+ * (CommonLib/InterPrediction.cpp:768-867, :960-1010), for a picture's worth of blocks of MIXED sizes in ONE launch — luma and 4:2:0 chroma, uni- and bi-predicted —
+ * and, on request, the residual against the original.  A picture-level entry like the plans: the caller has the vectors (DMVR results, merge candidates, the winners of a
+ * motion-search plan) and hands over the list; no per-PU call site of the encoder is involved.
+ *   item      : one component block.  width / height independent powers of two, luma 4..128, chroma 2..64.  Per reference list l (ref_plane[l] = index into the plane
+ *               table, -1 = list not used): ref_off[l] = the block's integer position ( mv >> shift ) in that plane, frac[l] = ( x, y ) fraction — 1/16 sample for luma,
+ *               1/32 for 4:2:0 chroma (shiftHor = MV_FRACTIONAL_BITS_INTERNAL + 1, :777-785).
+ *   luma      : the passes of vvhip_interp_luma_batch with filter_mode 0 — 8-tap m_lumaFilter, m_lumaFilter4x4 for 4x4 blocks, m_lumaAltHpelIFilter at phase 8 with
+ *               alt_hpel (IMV_HPEL); horizontal only / vertical only / both with the 14-bit intermediate.
+ *   chroma    : 4-tap m_chromaFilter, vFilterSize = NTAPS_CHROMA (:860-865): horizontal pass over height + 3 rows starting one row above the block, then vertical.
+ *   one list  : rndRes = 1 — final samples clipped to the bit depth.
+ *   two lists : both interpolated to the 14-bit intermediate (rndRes = 0), then the default weighted average AreaBuf<Pel>::addAvg (CommonLib/Buffer.cpp:549-575, core
+ *               :129-141): ClipPel( ( a + b + offset ) >> shiftNum ), shiftNum = max( 2, IF_INTERNAL_PREC - bitDepth ) + 1, offset = ( 1 << ( shiftNum - 1 ) ) + 2 * IF_INTERNAL_OFFS.
+ *               The two intermediates never leave the compute unit.
+ *   output    : pred_stride == 0: compact blocks (row pitch = width) at d_pred + dst_off; pred_stride > 0: the block's position dst_off in a plane of that row pitch.
+ *   residual  : with d_org and d_resi given, org - pred (int16) is written to d_resi in the layout of the prediction (same dst_off, same pitch): compact blocks one
+ *               after the other are directly a d_resi of vvhip_tu_rdo_multi_strided with resi_strides_host[i] = width; with pred_stride > 0 a residual plane for
+ *               vvhip_tu_rdo_multi.  The original block sits at d_org + org_off, row pitch org_stride (one pitch per call: the components of a picture buffer
+ *               allocated with one pitch, or one call per component).
+ * items_host is a HOST array: the library sorts it into size classes (a wave never mixes shapes; small blocks share a wave — sixteen 4x4 luma blocks, thirty-two 2x2
+ * chroma blocks), cuts large blocks into tiles, deals the workgroups to the XCDs in horizontal picture bands and keeps the device copy of that schedule in the context — running the
+ * same list again (same items, same plane table) uploads nothing and allocates nothing.  Results do not depend on the order of the list.  Items must not overlap in the output.
+ * Margins: every reference plane must be readable 4 (luma) / 2 (chroma) samples beyond the block on all sides plus 16 bytes behind the last row touched (the window is
+ * fetched as aligned dwords), and needs an even row pitch; a zero fraction reads no rows above / below the block.
+ * Unsupported input (a size that is not a power of two or out of range, a plane index outside the table, both lists unused, a fraction out of range) returns VVHIP_E_ARG with a
+ * message before anything is launched.
+ * NOT done here (the caller's job, as before): BDOF; the padded-reference rule of DMVR (DMVR::xFinalPaddedMCForDMVR, CommonLib/InterPrediction.cpp:1189-1260: a refined
+ * sub-block's final prediction reads a padded copy of its PREFETCHED window, not the true plane — this entry is exact for DMVR sub-blocks whose refinement is zero and for every
+ * non-DMVR PU); BCW and explicit weighted prediction; GEO blending; affine / PROF; IBC; reference picture resampling; the chroma phases of 4:2:2 and 4:4:4.
+ * ====================================================================================================================== */
+typedef struct
+{
+  int32_t dst_off;            /* sample offset of the block in d_pred (and in d_resi)                                  */
+  int32_t org_off;            /* the block in the original plane (residual only)                                       */
+  int32_t ref_off[2];         /* integer position ( mv >> shift ) in the reference plane, per list                     */
+  int16_t frac[2][2];         /* ( x, y ) fraction per list: 1/16 sample luma, 1/32 chroma                             */
+  int16_t width, height;
+  int8_t  ref_plane[2];       /* index into the plane table, -1 = list not used                                        */
+  uint8_t chroma;             /* 0: luma taps, 1: chroma taps                                                          */
+  uint8_t alt_hpel;           /* luma: m_lumaAltHpelIFilter at phase 8                                                 */
+} vvhip_pred_item;            /* 32 bytes */
+VVHIP_API int vvhip_pred_inter_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes /* <= 16, as vvhip_me_plan_run takes it (stride > 0) */,
+                                      const vvhip_pred_item* items_host, int n, int bit_depth,
+                                      int16_t* d_pred, int pred_stride,
+                                      const int16_t* d_org /* may be NULL */, int org_stride, int16_t* d_resi /* may be NULL */ );
+/* The chroma twin of vvhip_interp_luma_batch: n blocks of ONE size (powers of two, 2..64) from one plane, items on the device (frac_x / frac_y in 1/32 sample, org_off unused),
+ * compact output d_out[i*w*h + y*w + x]; rnd_res 1 = final samples, 0 = the 14-bit intermediate a bi-prediction average consumes.  Margins as above.                            */
+VVHIP_API int vvhip_interp_chroma_batch( vvhip_ctx* ctx, const int16_t* d_ref, int ref_stride, const vvhip_subpel_item* d_items, int n,
+                                         int width, int height, int bit_depth, int rnd_res, int16_t* d_out );
+
 /* ROM accessors (host memory out): the tables the kernels use, for parity checks against
  * g_trCore* (CommonLib/RomTr.cpp:364-449) and getScanOrder (CommonLib/Rom.h:104).               */
 VVHIP_API int vvhip_get_tr_matrix_host( int tr_type, int log2_size, int16_t* host_out );
@@ -525,7 +576,9 @@ VVHIP_API int vvhip_mctf_filter_params( int qp, int bit_depth, double overall_st
  * reference's scan order), parametric sub-pel error surface.
  *   ref0_off / ref1_off : the sub-block's integer position for the merge vector of list 0 / 1 (mv >> 4), frac* = mv & 15
  *   result              : mvd = cu.mvdL0SubPu[num] in 1/16 sample (list 1 moves by -mvd), min_cost = the value the BDOF switch compares
- *                         with 2*dx*dy (:1386).  The final motion compensation stays with the caller (vvhip_interp_luma_batch).          */
+ *                         with 2*dx*dy (:1386).  The final motion compensation: sub-blocks whose refinement is zero go into a prediction list
+ *                         (vvhip_pred_inter_batch: luma + chroma, both lists, the average); a refined sub-block needs DMVR's padded-reference rule
+ *                         (xFinalPaddedMCForDMVR, :1189-1260) and BDOF, which stay with the caller.                                          */
 typedef struct { int32_t ref0_off, ref1_off; int16_t frac0_x, frac0_y, frac1_x, frac1_y; } vvhip_dmvr_item;
 typedef struct { int16_t mvd_x, mvd_y; int32_t pad; uint64_t min_cost; } vvhip_dmvr_result;
 VVHIP_API int vvhip_dmvr_refine_batch( vvhip_ctx* ctx, const int16_t* d_ref0, int stride0, const int16_t* d_ref1, int stride1,

@@ -1,0 +1,228 @@
+#!/usr/bin/env python3
+"""tools/pred_time.py — what the prediction-list entry (vvhip_pred_inter_batch, vvenc_amd/csrc/pred.hip) costs on a 1920x1080 picture.
+
+  python tools/pred_time.py [--rounds 9] [--reps 40] [--other-lib PATH] [--json PATH] [--quick]
+
+A. the path it generalises: a picture's worth of luma 16x16 uni-prediction blocks (120 x 67 = 8040, seeded vectors within +-8 samples, all 256 phases) through
+   vvhip_interp_luma_batch and through vvhip_pred_inter_batch — and, with --other-lib, through vvhip_interp_luma_batch of ANOTHER build of the library (the parent commit's)
+   in the same rounds.  The two outputs of this build are compared sample for sample first.
+B. the realistic list: a B picture's mix of prediction units — the fixed histogram PU_HIST below (synthetic: shaped like the motion-estimation records of the recorded 1080p
+   lists, most samples in 64x64 and 32x32 units, most units 16x16 and smaller), half of the units bi-predicted (seeded), luma + both 4:2:0 chroma blocks per unit, residual
+   output on.  Reported: time per picture, the bytes the algorithm reads and writes (per list the window (w + taps - 1) x (h + taps - 1), the original block, prediction and
+   residual blocks; 2 bytes per sample) and their fraction of the HBM peak, the host time of a first call (sort + schedule + upload) and of a repeated call (the list is
+   recognised).
+Every variant is recorded into a launch graph once and timed as `reps` graph launches between two host clock readings that end in a device synchronise, `rounds` times, the
+variants alternating inside a round; medians, minima and the spread ( max - min ) / median are printed.  --quick: one round of few launches (for a profiler run)."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+W, H = 1920, 1080
+HBM_PEAK = 8.0e12          # bytes / s (the figure bench.py's roofline uses)
+# luma prediction units of one B picture: (width, height) -> count.  1.80 of the picture's 2.07 M luma samples are inter-predicted.
+PU_HIST = {(64, 64): 150, (32, 32): 420, (64, 32): 60, (32, 64): 60, (32, 16): 160, (16, 32): 160, (16, 16): 900, (16, 8): 260, (8, 16): 260, (8, 8): 700, (8, 4): 120, (4, 8): 120}
+SEED = 20240
+
+
+class OtherBuild:
+    """vvhip_interp_luma_batch of another build of the library, through its own context (its own stream)"""
+
+    def __init__(self, path, device):
+        vp, i32 = C.c_void_p, C.c_int
+        self.L = L = C.CDLL(path)
+        L.vvhip_create.argtypes = [C.POINTER(vp), i32]
+        L.vvhip_destroy.argtypes = [vp]
+        L.vvhip_destroy.restype = None
+        L.vvhip_last_error.restype = C.c_char_p
+        L.vvhip_last_error.argtypes = [vp]
+        for n in ("vvhip_use_own_stream", "vvhip_sync", "vvhip_graph_begin"):
+            getattr(L, n).argtypes = [vp]
+        L.vvhip_graph_end.argtypes = [vp, vp]
+        L.vvhip_graph_launch.argtypes = [vp, vp]
+        L.vvhip_interp_luma_batch.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+        self.ctx = vp()
+        self.ck(L.vvhip_create(C.byref(self.ctx), device))
+        self.ck(L.vvhip_use_own_stream(self.ctx))
+
+    def ck(self, rc):
+        if rc:
+            raise RuntimeError("other build: error %d: %s" % (rc, self.L.vvhip_last_error(self.ctx).decode()))
+
+    def capture(self, fn):
+        fn()
+        self.ck(self.L.vvhip_sync(self.ctx))
+        self.ck(self.L.vvhip_graph_begin(self.ctx))
+        fn()
+        g = C.c_void_p()
+        self.ck(self.L.vvhip_graph_end(self.ctx, C.byref(g)))
+        return g
+
+    def run(self, g, reps):
+        for _ in range(reps):
+            self.ck(self.L.vvhip_graph_launch(self.ctx, g))
+        self.ck(self.L.vvhip_sync(self.ctx))
+
+
+def chroma_of(y, k):
+    return np.clip((y[::2, ::2].astype(np.int32) * (3 + k)) // 4 + 60 * k, 0, 1023).astype(np.int16)
+
+
+def luma16_items(rng, stride):
+    from vvenc_amd.hotpath import PRED_ITEM_DTYPE, SUBPEL_DTYPE
+    bx, by = np.meshgrid(np.arange(W // 16), np.arange(H // 16))
+    n = bx.size
+    mvx, mvy = rng.integers(-8 * 16, 8 * 16 + 1, n), rng.integers(-8 * 16, 8 * 16 + 1, n)
+    x, y = bx.ravel() * 16 + (mvx >> 4), by.ravel() * 16 + (mvy >> 4)
+    sp = np.zeros(n, SUBPEL_DTYPE)
+    sp["ref_off"], sp["frac_x"], sp["frac_y"] = y * stride + x, mvx & 15, mvy & 15
+    it = np.zeros(n, PRED_ITEM_DTYPE)
+    it["dst_off"], it["width"], it["height"] = np.arange(n) * 256, 16, 16
+    it["ref_off"][:, 0], it["frac"][:, 0, 0], it["frac"][:, 0, 1] = sp["ref_off"], sp["frac_x"], sp["frac_y"]
+    it["ref_plane"][:, 0], it["ref_plane"][:, 1] = 0, -1
+    return sp, it
+
+
+def b_picture_items(rng, luma_stride, chroma_stride, org_stride):
+    """luma + Cb + Cr items of every unit of PU_HIST; planes 0 / 1: luma of list 0 / 1, 2 / 3: Cb, 4 / 5: Cr; the original picture is ONE buffer of row pitch org_stride
+    (Y on top, Cb and Cr side by side below it).  -> (items, algorithmic bytes read, written)"""
+    from vvenc_amd.hotpath import PRED_ITEM_DTYPE
+    recs, at, rd, wr = [], 0, 0, 0
+    for (w, h), count in PU_HIST.items():
+        for _ in range(count):
+            px, py = int(rng.integers(0, (W - w) // w + 1)) * w, int(rng.integers(0, (H - h) // h + 1)) * h
+            bi = bool(rng.integers(0, 2))
+            first = int(rng.integers(0, 2))
+            mv = [(int(rng.integers(-128, 129)), int(rng.integers(-128, 129))) for _ in range(2)]
+            for comp in range(3):
+                cs = 1 if comp else 0
+                it = np.zeros(1, PRED_ITEM_DTYPE)
+                cw, chh, cx, cy = w >> cs, h >> cs, px >> cs, py >> cs
+                it["width"], it["height"], it["chroma"], it["dst_off"] = cw, chh, cs, at
+                it["org_off"] = cy * org_stride + cx if comp == 0 else (H + cy) * org_stride + (comp - 1) * (W // 2) + cx
+                taps = 4 if cs else 8
+                for l in (0, 1):
+                    if not bi and l != first:
+                        it["ref_plane"][0, l] = -1
+                        continue
+                    sh, stride = 4 + cs, chroma_stride if cs else luma_stride
+                    it["ref_plane"][0, l] = 2 * comp + l
+                    it["ref_off"][0, l] = (cy + (mv[l][1] >> sh)) * stride + cx + (mv[l][0] >> sh)
+                    it["frac"][0, l] = (mv[l][0] & ((1 << sh) - 1), mv[l][1] & ((1 << sh) - 1))
+                    rd += 2 * (cw + taps - 1) * (chh + taps - 1)
+                rd += 2 * cw * chh
+                wr += 4 * cw * chh
+                at += cw * chh
+                recs.append(it)
+    items = np.concatenate(recs)
+    return items[rng.permutation(len(items))], at, rd, wr
+
+
+def stats(ts):
+    ts = sorted(ts)
+    med = ts[len(ts) // 2]
+    return {"median_us": round(med * 1e6, 2), "min_us": round(ts[0] * 1e6, 2), "spread": round((ts[-1] - ts[0]) / med, 4), "rounds": len(ts)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--reps", type=int, default=40)
+    ap.add_argument("--other-lib", default=None, help="another build of libvvenc_hip.so: its vvhip_interp_luma_batch is timed in the same rounds")
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--quick", action="store_true")
+    a = ap.parse_args()
+    if a.quick:
+        a.rounds, a.reps = 1, 5
+    import torch
+    from vvenc_amd.hotpath import HotPath
+    from vvenc_amd.workload import synth_frame_pair
+    hp = HotPath()
+    rng = np.random.default_rng(SEED)
+    y0, y1 = synth_frame_pair(W, H, SEED)
+    PAD = 32
+    luma = [hp.plane(y0, PAD), hp.plane(y1, PAD)]
+    chroma = [hp.plane(chroma_of(y, k), PAD) for k in (0, 1) for y in (y0, y1)]          # Cb list 0, Cb list 1, Cr list 0, Cr list 1
+    planes = luma + chroma
+    org_np = np.zeros((H + H // 2, W), np.int16)
+    org_np[:H] = np.clip(y0.astype(np.int32) + rng.integers(-9, 10, y0.shape), 0, 1023)
+    org_np[H:, :W // 2], org_np[H:, W // 2:] = chroma_of(y1, 0), chroma_of(y1, 1)
+    org = hp.plane(org_np, 0)
+    res = {"picture": [W, H], "rounds": a.rounds, "reps": a.reps}
+
+    # ---- A: luma 16x16 uni-prediction, old entry / new entry / the other build's old entry
+    sp, it = luma16_items(rng, luma[0].stride)
+    n = len(sp)
+    d_sp = hp.to_device(sp)
+    out_old = torch.zeros(n * 256, dtype=torch.int16, device=hp.device)
+    out_new = torch.zeros(n * 256, dtype=torch.int16, device=hp.device)
+    out_oth = torch.zeros(n * 256, dtype=torch.int16, device=hp.device)
+    hp.use_own_stream()          # warm-up (scratch, schedule upload) on the stream the graphs are recorded on
+    old_fn = lambda: hp.interp_luma_batch(luma[0], d_sp, n, 16, 16, 10, True, 0, False, out=out_old)
+    new_fn = lambda: hp.pred_inter_batch(planes[:1], it, out_new, 0, 10)
+    old_fn(); new_fn(); hp.sync()
+    assert torch.equal(out_old, out_new), "old and new entry disagree"
+    variants = {"interp_luma_batch": hp.graph_capture(old_fn), "pred_inter_batch": hp.graph_capture(new_fn)}
+    other = None
+    if a.other_lib:
+        other = OtherBuild(a.other_lib, hp.device.index or 0)
+        vp = C.c_void_p
+        g_oth = other.capture(lambda: other.ck(other.L.vvhip_interp_luma_batch(other.ctx, luma[0].buf_ptr, luma[0].stride, vp(d_sp.data_ptr()), n, 16, 16, 10, 1, 0, 0, vp(out_oth.data_ptr()))))
+        assert torch.equal(out_old, out_oth), "the other build's vvhip_interp_luma_batch disagrees"
+
+    def run(name, reps):
+        t0 = time.perf_counter()
+        if name == "other_build.interp_luma_batch":
+            other.run(g_oth, reps)
+        else:
+            for _ in range(reps):
+                hp.graph_launch(variants[name])
+            torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps
+
+    names = list(variants) + (["other_build.interp_luma_batch"] if other else [])
+    times = {k: [] for k in names}
+    for k in names:
+        run(k, 5)
+    for r in range(a.rounds):
+        for k in (names if r % 2 == 0 else names[::-1]):
+            times[k].append(run(k, a.reps))
+    res["luma16x16_uni"] = {"items": n, **{k: stats(v) for k, v in times.items()}}
+
+    # ---- B: the B picture's mix, residual on
+    items, total, rd, wr = b_picture_items(rng, luma[0].stride, chroma[0].stride, org.stride)
+    table = [luma[0], luma[1], chroma[0], chroma[1], chroma[2], chroma[3]]
+    pred = torch.zeros(total, dtype=torch.int16, device=hp.device)
+    resi = torch.zeros(total, dtype=torch.int16, device=hp.device)
+    mix_fn = lambda: hp.pred_inter_batch(table, items, pred, 0, 10, org, resi)
+    hp.use_own_stream()
+    t0 = time.perf_counter(); mix_fn(); host_first = time.perf_counter() - t0
+    hp.sync()
+    t0 = time.perf_counter(); mix_fn(); host_again = time.perf_counter() - t0
+    hp.sync()
+    g_mix = hp.graph_capture(mix_fn)
+    variants["b_picture"] = g_mix
+    run("b_picture", 5)
+    tm = [run("b_picture", a.reps) for _ in range(a.rounds)]
+    st = stats(tm)
+    sec = st["median_us"] * 1e-6
+    res["b_picture_mix"] = {"units": int(sum(PU_HIST.values())), "items": int(len(items)), "bi_items": int(((items["ref_plane"][:, 0] >= 0) & (items["ref_plane"][:, 1] >= 0)).sum()),
+                            "samples": int(total), **st, "bytes_read": int(rd), "bytes_written": int(wr), "achieved_GBps": round((rd + wr) / sec / 1e9, 1),
+                            "hbm_peak_fraction": round((rd + wr) / sec / HBM_PEAK, 4), "host_first_call_us": round(host_first * 1e6, 1), "host_repeated_call_us": round(host_again * 1e6, 1)}
+    for k, v in res.items():
+        print(k, json.dumps(v) if isinstance(v, dict) else v)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

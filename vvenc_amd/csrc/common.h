@@ -40,6 +40,16 @@ struct vvhip_ctx
   hipStream_t  tuGenStream = nullptr;      // the stream the cached generic-TU job table was uploaded on (trquant.hip: tuRdoMulti); compared only, never used as a handle
   hipEvent_t   tuGenEvent  = nullptr;      // recorded behind every launch that reads the table: a caller that switches streams orders the new stream behind it
   bool         tuGenEventRecorded = false;
+  // device copy of the schedule of vvhip_pred_inter_batch (pred.hip), the caller's list it was derived from (items + plane table: a list that is run again is neither sorted
+  // nor uploaded again) and the host copy the asynchronous upload reads
+  void*        d_predSched = nullptr;
+  size_t       predBytes  = 0;
+  std::vector<unsigned char> predKey, predBlob;
+  size_t       predOffSubs = 0, predOffUnits = 0;
+  int          predUnits  = 0, predLdsPerWave = 0;
+  hipStream_t  predStream = nullptr;       // the stream the schedule was uploaded on; compared only, never used as a handle
+  hipEvent_t   predEvent  = nullptr;       // recorded behind every launch that reads the schedule
+  bool         predEventRecorded = false;
   // how the host waits for the stream (vvhip_set_blocking_sync): false = hipStreamSynchronize (the runtime's low-latency wait), true = a blocking event — the calling thread
   // sleeps, which matters when the host's cores are all busy encoding
   bool         blockingSync = false;

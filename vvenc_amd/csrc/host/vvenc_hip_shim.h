@@ -220,6 +220,9 @@ struct QuantOps
 };
 
 // DMVR refinement search of one CU in one device call (DMVR::xProcessDMVR, CommonLib/InterPrediction.cpp:1262-1392).
+// What to do with the result: sub-blocks whose refinement is zero (and every PU that is not refined at all) can go straight into a prediction list
+// (InterPredOps::predictList: luma and chroma, both lists, the average); a sub-block with a non-zero refinement needs DMVR's padded-reference rule for its final
+// prediction (DMVR::xFinalPaddedMCForDMVR, :1189-1260) and BDOF where the cost switch leaves it on — both stay with the caller.
 struct DMVROps
 {
   // ref0 / ref1: the reference samples at the CU's position displaced by the integer part of the (clipped) merge vectors MINUS 2 samples in
@@ -227,6 +230,18 @@ struct DMVROps
   // Sub-blocks dx x dy (<= 16) in raster order: mvd[2*num], mvd[2*num+1] = cu.mvdL0SubPu[num]; minCost[num] = the value compared with 2*dx*dy (:1386).
   bool refineCu( const Pel* ref0, int stride0, int fx0, int fy0, const Pel* ref1, int stride1, int fx1, int fy1, int cuWidth, int cuHeight, int dx, int dy, int bitDepth,
                  int16_t* mvd, uint64_t* minCost );
+};
+
+// Inter prediction of a list of prediction units in one device call (vvhip_pred_inter_batch): InterPredInterpolation::xPredInterBlk + xWeightedAverage
+// (CommonLib/InterPrediction.cpp:768-867, :960-1010) for every component block of the list — luma and 4:2:0 chroma, one or two reference lists, any mix of sizes.
+struct InterPredOps
+{
+  // refPlanes[k]: host pointer to sample (0,0) of a plane that lies inside a picture registered with Device::registerPicture (reference pictures: setReference) — its mirror is
+  // read, nothing is uploaded but the list.  items: vvhip_pred_item records whose ref_plane indexes refPlanes, ref_off in samples at the picture's own line pitch, dst_off the
+  // block's place in the compact outputs (row pitch = width).  pred: predElems samples.  org (may be nullptr; a registered picture like the references) + resi: also
+  // org - pred, laid out like pred; org_off at the picture's line pitch.  false: a plane is not registered on this GPU (nothing was run).  Throws like every table entry when
+  // the device rejects the list (vvhip::Exception with the entry's message).
+  bool predictList( const Pel* const* refPlanes, int numPlanes, const vvhip_pred_item* items, int n, int bitDepth, Pel* pred, size_t predElems, const Pel* org = nullptr, Pel* resi = nullptr );
 };
 
 // ALF encoder statistics: whole-plane forms of AdaptiveLoopFilter::m_deriveClassificationBlk (CommonLib/AdaptiveLoopFilter.h,

@@ -1,0 +1,519 @@
+// pred.hip — inter prediction of a LIST of prediction units: luma and 4:2:0 chroma, uni- and bi-predicted, every block size in one launch,
+// optionally with the residual against the original.
+//
+// Reference behaviour (all integer, bit-exact):
+//   InterPredInterpolation::xPredInterBlk (fractions, which passes run)   CommonLib/InterPrediction.cpp:768-867
+//   InterPredInterpolation::xWeightedAverage -> AreaBuf<Pel>::addAvg        :960-1010, CommonLib/Buffer.cpp:549-575 (core :129-141)
+//   InterpolationFilter::filter<N,isVertical,isFirst,isLast> / filterCopy   CommonLib/InterpolationFilter.cpp:356-441, :255-333
+//
+// One wave takes one unit of the schedule the host derives from the list: a tile of a large block, or several whole small blocks of ONE size class
+// (a 4x4 luma block occupies 4 lanes, a 2x2 chroma block 2: sixteen / thirty-two blocks per wave).  Per reference list a lane group
+//   1. stages the tile's reference window in LDS (aligned dwords from HBM; only the rows / columns the two fractions reach),
+//   2. runs the horizontal pass over the window rows into a 14-bit intermediate in LDS (isFirst, !isLast),
+//   3. runs the vertical pass from it into registers (!isFirst; isLast for a uni-predicted block).
+// A zero fraction takes the same two passes with the one-tap set { 64 }: the copy forms of the reference give the same values, and so does its single-pass dispatch for a
+// vector with one zero fraction (floor( ( floor( a / 4 ) + b ) / c ) = floor( ( a + 4 b ) / ( 4 c ) ) for integers — the rule interp.hip's refinement kernel already relies on).
+// A bi-predicted block keeps list 0's 14-bit block in registers while list 1 goes through the same LDS, then averages: the two intermediates never leave the wave.
+// Waves synchronise with themselves only (no workgroup barrier); a workgroup is four independent waves.
+#include <algorithm>
+#include <string.h>
+#include "common.h"
+
+namespace {
+
+// VVC tap sets, phases 0..P/2; row P-p is row p reversed (InterpolationFilter.cpp:64-142)
+__constant__ int8_t cPLuma8[9][8] = {
+  { 0, 0, 0, 64, 0, 0, 0, 0 }, { 0, 1, -3, 63, 4, -2, 1, 0 }, { -1, 2, -5, 62, 8, -3, 1, 0 }, { -1, 3, -8, 60, 13, -4, 1, 0 }, { -1, 4, -10, 58, 17, -5, 1, 0 },
+  { -1, 4, -11, 52, 26, -8, 3, -1 }, { -1, 3, -9, 47, 31, -10, 4, -1 }, { -1, 4, -11, 45, 34, -10, 4, -1 }, { -1, 4, -11, 40, 40, -11, 4, -1 } };
+__constant__ int8_t cPLuma6[9][8] = {
+  { 0, 0, 0, 64, 0, 0, 0, 0 }, { 0, 1, -3, 63, 4, -2, 1, 0 }, { 0, 1, -5, 62, 8, -3, 1, 0 }, { 0, 2, -8, 60, 13, -4, 1, 0 }, { 0, 3, -10, 58, 17, -5, 1, 0 },
+  { 0, 3, -11, 52, 26, -8, 2, 0 }, { 0, 2, -9, 47, 31, -10, 3, 0 }, { 0, 3, -11, 45, 34, -10, 3, 0 }, { 0, 3, -11, 40, 40, -11, 3, 0 } };
+__constant__ int8_t cPAltHpel[8] = { 0, 3, 9, 20, 20, 9, 3, 0 };
+__constant__ int8_t cPChroma4[17][4] = {
+  { 0, 64, 0, 0 }, { -1, 63, 2, 0 }, { -2, 62, 4, 0 }, { -2, 60, 7, -1 }, { -2, 58, 10, -2 }, { -3, 57, 12, -2 }, { -4, 56, 14, -2 }, { -4, 55, 15, -2 }, { -4, 54, 16, -2 },
+  { -5, 53, 18, -2 }, { -6, 52, 20, -2 }, { -6, 49, 24, -3 }, { -6, 46, 28, -4 }, { -5, 44, 29, -4 }, { -4, 42, 30, -4 }, { -4, 39, 33, -4 }, { -4, 36, 36, -4 } };
+
+// ---- the schedule the host uploads ----
+struct __attribute__( ( aligned( 16 ) ) ) PredDev      // one prediction item with the plane table resolved
+{
+  const int16_t* ref[2];         // reference block at its integer position; null = list not used
+  int32_t stride[2];
+  int32_t dstOff, orgOff;
+  int16_t frac[2][2];
+  int16_t w, h;
+  uint8_t alt, pad[3];
+};
+struct PredSub  { int32_t item; int16_t x0, y0; };      // one tile of an item
+struct PredUnit { int32_t firstSub; int16_t nSub, tw, th; uint8_t kind, log2Lanes, log2SegsRow, pad[3]; };      // what one wave does
+static_assert( sizeof( PredDev ) == 48 && sizeof( PredSub ) == 8 && sizeof( PredUnit ) == 16, "schedule records" );
+
+// kernel forms: samples per lane (a "segment": SEG horizontally adjacent samples) x taps per pass
+enum { KIND_L8 = 0, KIND_L4 = 1, KIND_C8 = 2, KIND_C4 = 3, KIND_C2 = 4 };
+enum { MODE_UNI = 0, MODE_BI = 1, MODE_RAW = 2 };      // final samples of one list / average of two / the 14-bit block of one list (rnd_res = 0)
+
+struct TileShape { int tw, th, log2SegsRow, log2Lanes, kind; };
+inline int segOfKind( int kind ) { return kind == KIND_L8 || kind == KIND_C8 ? 8 : kind == KIND_C2 ? 2 : 4; }
+inline int tapsOfKind( int kind ) { return kind <= KIND_L4 ? 8 : 4; }
+
+// a block is cut into tiles of at most 64 segments: 32 x 16, 16 x 32, 8 x 64, 4 x 64, 2 x 64 — or the whole block when it is smaller
+TileShape tileShape( int w, int h, bool chroma )
+{
+  TileShape s;
+  const int seg = w >= 8 ? 8 : w;
+  s.kind = chroma ? ( seg == 8 ? KIND_C8 : seg == 4 ? KIND_C4 : KIND_C2 ) : ( seg == 8 ? KIND_L8 : KIND_L4 );
+  s.tw = std::min( w, 32 );
+  s.log2SegsRow = ilog2i( s.tw / seg );
+  s.th = std::min( h, 64 >> s.log2SegsRow );
+  s.log2Lanes = s.log2SegsRow + ilog2i( s.th );
+  return s;
+}
+// LDS samples of one tile: the window (row pitch tw + taps + 2) and the first-pass block, th + taps - 1 rows each, both 16-byte aligned
+__host__ __device__ inline int winElems( int tw, int th, int nt ) { return ( ( th + nt - 1 ) * ( tw + nt + 2 ) + 7 ) & ~7; }
+__host__ __device__ inline int subElems( int tw, int th, int nt ) { return winElems( tw, th, nt ) + ( ( ( th + nt - 1 ) * tw + 7 ) & ~7 ); }
+
+// what one lane needs to know about the tile its group works on
+struct Lane
+{
+  bool on;
+  const int16_t* ref[2];
+  int stride[2], fx[2], fy[2];
+  int w, h, alt;                 // the whole block (4x4 luma has its own tap set); alternative half-sample filter
+  int x0, y0;                    // tile origin inside the block
+  int lis;                       // lane inside the group
+  int mode;
+  int16_t* win; int16_t* tmp;
+  int16_t* dst; int dstPitch;    // block origin in the prediction buffer
+  const int16_t* org; int orgPitch;
+  int16_t* res; int resPitch;    // null: no residual
+};
+
+#define PRED_WAVE_SYNC() { __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" ); __builtin_amdgcn_wave_barrier(); }
+
+// taps of one direction as c[k] * sample[pos - lo + k]; a zero fraction is the one-tap set { 64 } at lo = 0
+template<int NT>
+__device__ __forceinline__ void loadTaps( int ( &c )[NT], int& lo, int frac, bool is4x4, bool both, int alt )
+{
+#pragma unroll
+  for( int k = 0; k < NT; k++ ) c[k] = 0;
+  lo = 0;
+  if( frac == 0 ) { c[0] = 64; return; }
+  lo = NT / 2 - 1;
+  if( NT == 8 )
+  {
+    // 4x4 blocks: filter4x4 swaps in the alternative row for BOTH directions whatever the phase (InterpolationFilter.cpp:692-693); the 1-D dispatch only at phase 8 (:570-580)
+    const bool useAlt = is4x4 ? ( alt && ( both || frac == 8 ) ) : ( alt && frac == 8 );
+    const int p = frac <= 8 ? frac : 16 - frac;
+#pragma unroll
+    for( int k = 0; k < NT; k++ )
+    {
+      const int kk = frac <= 8 ? k : 7 - k;
+      c[k] = useAlt ? cPAltHpel[k & 7] : is4x4 ? cPLuma6[p][kk & 7] : cPLuma8[p][kk & 7];
+    }
+  }
+  else
+  {
+#pragma unroll
+    for( int k = 0; k < NT; k++ ) c[k] = frac <= 16 ? cPChroma4[frac][k & 3] : cPChroma4[32 - frac][3 - ( k & 3 )];
+  }
+}
+
+template<int SEG> struct __attribute__( ( aligned( SEG * 2 ) ) ) SegRow { int16_t v[SEG]; };
+
+template<int SEG, int NT>
+__device__ __forceinline__ void predBody( const Lane& L, int tw, int th, int log2SegsRow, int lanes, int bitDepth )
+{
+  constexpr int ND = ( SEG + NT ) / 2 + 1;              // dwords that hold a segment's SEG + NT - 1 window samples at either alignment
+  const int hr = 14 - bitDepth > 2 ? 14 - bitDepth : 2, maxv = ( 1 << bitDepth ) - 1;
+  const int pitch = tw + NT + 2, segsRow = 1 << log2SegsRow;
+  const int y = L.lis >> log2SegsRow, xs = ( L.lis & ( segsRow - 1 ) ) * SEG;      // this lane's output row and first column inside the tile
+  const bool is4x4 = NT == 8 && L.w == 4 && L.h == 4;
+  int first[SEG], acc[SEG];
+#pragma unroll
+  for( int j = 0; j < SEG; j++ ) first[j] = acc[j] = 0;
+
+#pragma unroll
+  for( int l = 0; l < 2; l++ )
+  {
+    const bool use = L.on && L.ref[l] != nullptr;
+    const bool both = L.fx[l] != 0 && L.fy[l] != 0;
+    int ch[NT], cv[NT], loX = 0, loY = 0;
+    loadTaps<NT>( ch, loX, L.fx[l], is4x4, both, L.alt );
+    loadTaps<NT>( cv, loY, L.fy[l], is4x4, both, L.alt );
+    const int rows = th + ( L.fy[l] ? NT - 1 : 0 ), cols = tw + ( L.fx[l] ? NT - 1 : 0 );
+    int sh = 0;
+    // ---- 1. the window: rows y0 - loY .. , columns x0 - loX - sh .. as aligned dwords (sh = 1 when the first column sits in the upper half of its dword)
+    if( use )
+    {
+      const int16_t* g = L.ref[l] + ( ptrdiff_t ) ( L.y0 - loY ) * L.stride[l] + ( L.x0 - loX );
+      const uintptr_t a = reinterpret_cast<uintptr_t>( g );
+      sh = ( int ) ( ( a >> 1 ) & 1 );
+      const uint32_t* g32 = reinterpret_cast<const uint32_t*>( a & ~( uintptr_t ) 3 );
+      const int dwRow = ( cols + sh + 1 ) >> 1, strideDw = L.stride[l] >> 1;        // (the stride is even: every row has the same alignment)
+      uint32_t* w32 = reinterpret_cast<uint32_t*>( L.win );
+      const int l2 = 32 - __builtin_clz( ( unsigned ) ( dwRow - 1 ) | 1u );      // rows are dealt in strides of the next power of two: no division (a quarter of the slots idle at worst)
+      for( int i = L.lis; i < ( rows << l2 ); i += lanes )
+      {
+        const int r = i >> l2, d = i & ( ( 1 << l2 ) - 1 );
+        if( d < dwRow ) w32[r * ( pitch >> 1 ) + d] = g32[( ptrdiff_t ) r * strideDw + d];
+      }
+    }
+    PRED_WAVE_SYNC();
+    // ---- 2. horizontal pass, isFirst && !isLast: ( sum - ( 8192 << s1 ) ) >> s1 with s1 = 6 - headroom
+    if( use )
+    {
+      const int s1 = 6 - hr, off1 = -( 8192 << s1 );
+      for( int i = L.lis; i < ( rows << log2SegsRow ); i += lanes )
+      {
+        const int r = i >> log2SegsRow, x = ( i & ( segsRow - 1 ) ) * SEG;
+        const uint32_t* p = reinterpret_cast<const uint32_t*>( L.win + r * pitch + x );
+        uint32_t d[ND];
+#pragma unroll
+        for( int k = 0; k < ND; k++ ) d[k] = p[k];
+        int win[SEG + NT];
+#pragma unroll
+        for( int k = 0; k < ND - 1; k++ )
+        {
+          const uint32_t s = __builtin_amdgcn_alignbit( d[k + 1], d[k], ( uint32_t ) ( sh << 4 ) );
+          win[2 * k] = ( int ) ( int16_t ) ( s & 0xffff ); win[2 * k + 1] = ( int ) ( int16_t ) ( s >> 16 );
+        }
+        SegRow<SEG> o;
+#pragma unroll
+        for( int j = 0; j < SEG; j++ )
+        {
+          int s = 0;
+#pragma unroll
+          for( int k = 0; k < NT; k++ ) s = __mul24( win[j + k], ch[k] ) + s;       // |sample| < 2^15, |tap| < 2^7: the 24-bit multiply is exact
+          o.v[j] = ( int16_t ) ( ( s + off1 ) >> s1 );
+        }
+        *reinterpret_cast<SegRow<SEG>*>( L.tmp + r * tw + x ) = o;
+      }
+    }
+    PRED_WAVE_SYNC();
+    // ---- 3. vertical pass, !isFirst: isLast ( + clip ) for a uni-predicted block, the 14-bit block otherwise
+    if( use )
+    {
+#pragma unroll
+      for( int j = 0; j < SEG; j++ ) acc[j] = 0;
+#pragma unroll
+      for( int k = 0; k < NT; k++ )
+      {
+        const SegRow<SEG> row = *reinterpret_cast<const SegRow<SEG>*>( L.tmp + ( y + k ) * tw + xs );
+#pragma unroll
+        for( int j = 0; j < SEG; j++ ) acc[j] = __mul24( ( int ) row.v[j], cv[k] ) + acc[j];
+      }
+      if( L.mode == MODE_UNI )
+      {
+        const int s2 = 6 + hr, off2 = ( 1 << ( s2 - 1 ) ) + ( 8192 << 6 );
+#pragma unroll
+        for( int j = 0; j < SEG; j++ ) { const int v = ( int16_t ) ( ( acc[j] + off2 ) >> s2 ); acc[j] = v < 0 ? 0 : ( v > maxv ? maxv : v ); }
+      }
+      else
+      {
+#pragma unroll
+        for( int j = 0; j < SEG; j++ ) acc[j] = ( int16_t ) ( acc[j] >> 6 );
+      }
+    }
+    PRED_WAVE_SYNC();
+    if( l == 0 )
+    {
+#pragma unroll
+      for( int j = 0; j < SEG; j++ ) first[j] = acc[j];
+    }
+  }
+  if( !L.on ) return;
+  if( L.mode == MODE_BI )      // addAvg: ClipPel( ( a + b + offset ) >> shiftNum ), shiftNum = headroom + 1, offset = ( 1 << headroom ) + 2 * IF_INTERNAL_OFFS (Buffer.cpp:129-141, :549-575)
+  {
+    const int sn = hr + 1, off = ( 1 << hr ) + 2 * 8192;
+#pragma unroll
+    for( int j = 0; j < SEG; j++ ) { const int v = ( first[j] + acc[j] + off ) >> sn; acc[j] = v < 0 ? 0 : ( v > maxv ? maxv : v ); }
+  }
+  else if( L.ref[1] == nullptr )
+  {
+#pragma unroll
+    for( int j = 0; j < SEG; j++ ) acc[j] = first[j];
+  }
+  const int row = L.y0 + y, col = L.x0 + xs;
+  SegRow<SEG> o;
+#pragma unroll
+  for( int j = 0; j < SEG; j++ ) o.v[j] = ( int16_t ) acc[j];
+  int16_t* dp = L.dst + ( ptrdiff_t ) row * L.dstPitch + col;
+  if( ( reinterpret_cast<uintptr_t>( dp ) & ( SEG * 2 - 1 ) ) == 0 ) *reinterpret_cast<SegRow<SEG>*>( dp ) = o;
+  else
+  {
+#pragma unroll
+    for( int j = 0; j < SEG; j++ ) dp[j] = o.v[j];
+  }
+  if( L.res )
+  {
+    const int16_t* op = L.org + ( ptrdiff_t ) row * L.orgPitch + col;
+    SegRow<SEG> g;
+    if( ( reinterpret_cast<uintptr_t>( op ) & ( SEG * 2 - 1 ) ) == 0 ) g = *reinterpret_cast<const SegRow<SEG>*>( op );
+    else
+    {
+#pragma unroll
+      for( int j = 0; j < SEG; j++ ) g.v[j] = op[j];
+    }
+#pragma unroll
+    for( int j = 0; j < SEG; j++ ) g.v[j] = ( int16_t ) ( g.v[j] - o.v[j] );
+    int16_t* rp = L.res + ( ptrdiff_t ) row * L.resPitch + col;
+    if( ( reinterpret_cast<uintptr_t>( rp ) & ( SEG * 2 - 1 ) ) == 0 ) *reinterpret_cast<SegRow<SEG>*>( rp ) = g;
+    else
+    {
+#pragma unroll
+      for( int j = 0; j < SEG; j++ ) rp[j] = g.v[j];
+    }
+  }
+}
+
+__device__ __forceinline__ void predDispatch( int kind, const Lane& L, int tw, int th, int log2SegsRow, int lanes, int bitDepth )
+{
+  switch( kind )      // wave-uniform
+  {
+  case KIND_L8: predBody<8, 8>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_L4: predBody<4, 8>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_C8: predBody<8, 4>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_C4: predBody<4, 4>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  default:      predBody<2, 4>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  }
+}
+
+struct PredArgs
+{
+  const PredDev* items; const PredSub* subs; const PredUnit* units;
+  int nUnits, bitDepth, ldsPerWave;
+  int16_t* pred; int predStride;
+  const int16_t* org; int orgStride;
+  int16_t* resi;
+};
+
+// a list of mixed sizes: wave -> unit of the host's schedule (size classes, picture bands per XCD)
+__global__ void __launch_bounds__( 256 )
+predListKernel( PredArgs a )
+{
+  extern __shared__ __attribute__( ( aligned( 16 ) ) ) int16_t sPred[];
+  const int wave = __builtin_amdgcn_readfirstlane( ( int ) ( threadIdx.x >> 6 ) ), lane = threadIdx.x & 63;
+  const int ui = ( int ) blockIdx.x * 4 + wave;
+  if( ui >= a.nUnits ) return;
+  const PredUnit u = a.units[ui];
+  if( u.nSub == 0 ) return;
+  const int nt = u.kind <= KIND_L4 ? 8 : 4, lanes = 1 << u.log2Lanes, si = lane >> u.log2Lanes;
+  Lane L;
+  L.on = si < u.nSub;
+  L.lis = lane & ( lanes - 1 );
+  L.win = sPred + ( size_t ) wave * a.ldsPerWave + ( size_t ) si * subElems( u.tw, u.th, nt );
+  L.tmp = L.win + winElems( u.tw, u.th, nt );
+  const PredSub s = a.subs[u.firstSub + ( L.on ? si : 0 )];
+  const PredDev it = a.items[s.item];
+  L.ref[0] = it.ref[0]; L.ref[1] = it.ref[1]; L.stride[0] = it.stride[0]; L.stride[1] = it.stride[1];
+  L.fx[0] = it.frac[0][0]; L.fy[0] = it.frac[0][1]; L.fx[1] = it.frac[1][0]; L.fy[1] = it.frac[1][1];
+  L.w = it.w; L.h = it.h; L.alt = it.alt; L.x0 = s.x0; L.y0 = s.y0;
+  L.mode = it.ref[0] && it.ref[1] ? MODE_BI : MODE_UNI;
+  if( !it.ref[0] ) { L.ref[0] = it.ref[1]; L.stride[0] = it.stride[1]; L.fx[0] = L.fx[1]; L.fy[0] = L.fy[1]; L.ref[1] = nullptr; }      // a list-1-only block runs as the first pass
+  L.dstPitch = a.predStride ? a.predStride : it.w;
+  L.dst = a.pred + it.dstOff;
+  L.org = a.org ? a.org + it.orgOff : nullptr; L.orgPitch = a.orgStride;
+  L.res = a.resi ? a.resi + it.dstOff : nullptr; L.resPitch = L.dstPitch;
+  predDispatch( u.kind, L, u.tw, u.th, u.log2SegsRow, lanes, a.bitDepth );
+}
+
+// one block size per call, items on the device (the chroma twin of vvhip_interp_luma_batch): tile g of the launch is tile g % tilesPerItem of item g / tilesPerItem
+__global__ void __launch_bounds__( 256 )
+predOneSizeKernel( const int16_t* __restrict__ ref, int refStride, const vvhip_subpel_item* __restrict__ items, int n, int w, int h, int bitDepth, int rndRes,
+                   int kind, int tw, int th, int log2SegsRow, int log2Lanes, int ldsPerWave, int16_t* __restrict__ out )
+{
+  extern __shared__ __attribute__( ( aligned( 16 ) ) ) int16_t sPred[];
+  const int wave = __builtin_amdgcn_readfirstlane( ( int ) ( threadIdx.x >> 6 ) ), lane = threadIdx.x & 63;
+  const int lanes = 1 << log2Lanes, si = lane >> log2Lanes, tilesX = w / tw, tilesPerItem = tilesX * ( h / th );
+  const long long g = ( ( long long ) blockIdx.x * 4 + wave ) * ( 64 >> log2Lanes ) + si;
+  if( ( ( long long ) blockIdx.x * 4 + wave ) * ( 64 >> log2Lanes ) >= ( long long ) n * tilesPerItem ) return;
+  Lane L;
+  L.on = g < ( long long ) n * tilesPerItem;
+  const int item = L.on ? ( int ) ( g / tilesPerItem ) : 0, t = L.on ? ( int ) ( g - ( long long ) item * tilesPerItem ) : 0;
+  const vvhip_subpel_item it = items[item];
+  L.lis = lane & ( lanes - 1 );
+  L.win = sPred + ( size_t ) wave * ldsPerWave + ( size_t ) si * subElems( tw, th, 4 );
+  L.tmp = L.win + winElems( tw, th, 4 );
+  L.ref[0] = ref + it.ref_off; L.ref[1] = nullptr; L.stride[0] = L.stride[1] = refStride;
+  L.fx[0] = it.frac_x & 31; L.fy[0] = it.frac_y & 31; L.fx[1] = L.fy[1] = 0;
+  L.w = w; L.h = h; L.alt = 0; L.x0 = ( t % tilesX ) * tw; L.y0 = ( t / tilesX ) * th;
+  L.mode = rndRes ? MODE_UNI : MODE_RAW;
+  L.dst = out + ( size_t ) item * w * h; L.dstPitch = w;
+  L.org = nullptr; L.orgPitch = 0; L.res = nullptr; L.resPitch = 0;
+  predDispatch( kind, L, tw, th, log2SegsRow, lanes, bitDepth );
+}
+
+// XCD-aware order of a class's workgroups (as me.hip's xcdBandOrder): workgroups are dealt round-robin to the 8 XCDs, each with a private L2; workgroup base + l of the launch
+// is handed the next entry of the ( ( base + l ) % 8 )-th contiguous eighth of the class, whose entries are sorted by picture position: every L2 streams one horizontal band.
+std::vector<int> predBandOrder( int nGroups, int base )
+{
+  std::vector<int> perm( nGroups );
+  const int q = ( nGroups + 7 ) / 8;
+  int cursor[8], endOf[8];
+  for( int x = 0; x < 8; x++ ) { cursor[x] = std::min( nGroups, x * q ); endOf[x] = std::min( nGroups, ( x + 1 ) * q ); }
+  for( int l = 0; l < nGroups; l++ )
+  {
+    int x = ( base + l ) & 7;
+    for( int t = 0; t < 8 && cursor[x] >= endOf[x]; t++ ) x = ( x + 1 ) & 7;
+    perm[l] = cursor[x]++;
+  }
+  return perm;
+}
+
+struct Keyed { uint32_t cls; int64_t pos; int idx; };
+
+// validates the list, derives the schedule and uploads it; on success the context's key names the list (items + plane table) the device copy belongs to
+int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, int n, std::vector<unsigned char>& key )
+{
+  // ---- validation + plane table resolved; nothing is launched when any item is unsupported
+  std::vector<PredDev> dev( n );
+  std::vector<Keyed> order( n );
+  for( int i = 0; i < n; i++ )
+  {
+    const vvhip_pred_item& it = items_host[i];
+    const int lo = it.chroma ? 2 : 4, hi = it.chroma ? 64 : 128, fmax = it.chroma ? 32 : 16;
+    if( it.chroma > 1 || !isPow2( it.width ) || !isPow2( it.height ) || it.width < lo || it.height < lo || it.width > hi || it.height > hi )
+      return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch: item %d: %s block %dx%d (width and height powers of two, luma 4..128, chroma 2..64)", i, it.chroma ? "chroma" : "luma", it.width, it.height );
+    if( it.ref_plane[0] < 0 && it.ref_plane[1] < 0 ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch: item %d uses neither reference list", i );
+    if( it.alt_hpel && it.chroma ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch: item %d: the alternative half-sample filter is a luma filter", i );
+    PredDev& d = dev[i];
+    memset( &d, 0, sizeof( d ) );
+    for( int l = 0; l < 2; l++ )
+    {
+      if( it.ref_plane[l] < 0 ) continue;
+      if( it.ref_plane[l] >= n_planes || !planes_host[it.ref_plane[l]].d_base )
+        return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch: item %d: list %d names plane %d of a table of %d", i, l, it.ref_plane[l], n_planes );
+      if( it.frac[l][0] < 0 || it.frac[l][0] >= fmax || it.frac[l][1] < 0 || it.frac[l][1] >= fmax )
+        return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch: item %d: list %d fraction (%d, %d) outside 0..%d", i, l, it.frac[l][0], it.frac[l][1], fmax - 1 );
+      d.ref[l] = planes_host[it.ref_plane[l]].d_base + it.ref_off[l];
+      d.stride[l] = planes_host[it.ref_plane[l]].stride;
+      d.frac[l][0] = it.frac[l][0]; d.frac[l][1] = it.frac[l][1];
+    }
+    d.dstOff = it.dst_off; d.orgOff = it.org_off; d.w = it.width; d.h = it.height; d.alt = it.alt_hpel ? 1 : 0;
+    // size class: the most samples first (their waves run longest), then shape, component and uni / bi — a wave never mixes classes; inside a class picture order
+    const bool bi = it.ref_plane[0] >= 0 && it.ref_plane[1] >= 0;
+    order[i].cls = ( ( uint32_t ) ( 14 - ilog2i( it.width ) - ilog2i( it.height ) ) << 8 ) | ( ( uint32_t ) ilog2i( it.width ) << 4 ) | ( it.chroma ? 2u : 0u ) | ( bi ? 1u : 0u );
+    const int l0 = it.ref_plane[0] >= 0 ? 0 : 1;
+    order[i].pos = ( ( int64_t ) it.ref_off[l0] << 5 ) | ( uint32_t ) ( it.ref_plane[l0] & 31 );
+    order[i].idx = i;
+  }
+  std::sort( order.begin(), order.end(), []( const Keyed& a, const Keyed& b ) { return a.cls != b.cls ? a.cls < b.cls : a.pos != b.pos ? a.pos < b.pos : a.idx < b.idx; } );
+
+  // ---- schedule: per class the tiles in picture order, 64 lanes' worth per wave, four waves per workgroup, workgroups dealt to the XCDs in bands
+  std::vector<PredSub> subs;
+  std::vector<PredUnit> units;
+  int ldsPerWave = 0;
+  for( int c0 = 0; c0 < n; )
+  {
+    int c1 = c0; while( c1 < n && order[c1].cls == order[c0].cls ) c1++;
+    const vvhip_pred_item& f = items_host[order[c0].idx];
+    const TileShape ts = tileShape( f.width, f.height, f.chroma != 0 );
+    const int subsPerWave = 64 >> ts.log2Lanes, nt = tapsOfKind( ts.kind );
+    ldsPerWave = std::max( ldsPerWave, subsPerWave * subElems( ts.tw, ts.th, nt ) );
+    const size_t firstSub = subs.size();
+    for( int k = c0; k < c1; k++ )
+      for( int y0 = 0; y0 < f.height; y0 += ts.th ) for( int x0 = 0; x0 < f.width; x0 += ts.tw ) subs.push_back( PredSub{ order[k].idx, ( int16_t ) x0, ( int16_t ) y0 } );
+    const int nSubs = ( int ) ( subs.size() - firstSub ), nWaves = ( nSubs + subsPerWave - 1 ) / subsPerWave, nWg = ( nWaves + 3 ) / 4;
+    const std::vector<int> perm = predBandOrder( nWg, ( int ) ( units.size() / 4 ) );
+    for( int l = 0; l < nWg; l++ ) for( int wv = 0; wv < 4; wv++ )
+    {
+      const int q = perm[l] * 4 + wv;
+      PredUnit u; memset( &u, 0, sizeof( u ) );
+      u.tw = ( int16_t ) ts.tw; u.th = ( int16_t ) ts.th; u.kind = ( uint8_t ) ts.kind; u.log2Lanes = ( uint8_t ) ts.log2Lanes; u.log2SegsRow = ( uint8_t ) ts.log2SegsRow;
+      if( q < nWaves ) { u.firstSub = ( int32_t ) ( firstSub + ( size_t ) q * subsPerWave ); u.nSub = ( int16_t ) std::min( subsPerWave, nSubs - q * subsPerWave ); }
+      units.push_back( u );
+    }
+    c0 = c1;
+  }
+
+  // ---- device copy of the schedule: grow-only; the host copy stays alive as the source of the asynchronous upload
+  const size_t bItems = ( dev.size() * sizeof( PredDev ) + 255 ) & ~( size_t ) 255, bSubs = ( subs.size() * sizeof( PredSub ) + 255 ) & ~( size_t ) 255, bUnits = units.size() * sizeof( PredUnit );
+  if( ctx->predEventRecorded ) VVHIP_CHECK_HIP( ctx, hipEventSynchronize( ctx->predEvent ) );      // the last launch that reads the old schedule, whatever stream it went to
+  ctx->predKey.clear();
+  if( bItems + bSubs + bUnits > ctx->predBytes )
+  {
+    if( ctx->d_predSched ) ( void ) hipFree( ctx->d_predSched );
+    ctx->d_predSched = nullptr; ctx->predBytes = 0;
+    const size_t want = ( bItems + bSubs + bUnits ) + ( bItems + bSubs + bUnits ) / 4;
+    VVHIP_CHECK_HIP( ctx, hipMalloc( &ctx->d_predSched, want ) );
+    ctx->predBytes = want;
+  }
+  ctx->predBlob.assign( bItems + bSubs + bUnits, 0 );
+  memcpy( ctx->predBlob.data(), dev.data(), dev.size() * sizeof( PredDev ) );
+  memcpy( ctx->predBlob.data() + bItems, subs.data(), subs.size() * sizeof( PredSub ) );
+  memcpy( ctx->predBlob.data() + bItems + bSubs, units.data(), bUnits );
+  VVHIP_CHECK_HIP( ctx, hipMemcpyAsync( ctx->d_predSched, ctx->predBlob.data(), ctx->predBlob.size(), hipMemcpyHostToDevice, ctx->stream ) );
+  ctx->predStream = ctx->stream;
+  ctx->predOffSubs = bItems; ctx->predOffUnits = bItems + bSubs; ctx->predUnits = ( int ) units.size(); ctx->predLdsPerWave = ldsPerWave;
+  ctx->predKey.swap( key );
+  return VVHIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int vvhip_pred_inter_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, int n, int bit_depth,
+                            int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
+{
+  if( !ctx ) return VVHIP_E_ARG;
+  if( !planes_host || n_planes < 1 || n_planes > 16 || n < 0 || n > ( 1 << 24 ) || bit_depth < 8 || bit_depth > 12 || pred_stride < 0 || ( n && ( !items_host || !d_pred ) ) || ( d_resi && !d_org ) )
+    return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch: %d planes (1..16), %d items, bitDepth %d, prediction %p pitch %d, original %p, residual %p", n_planes, n, bit_depth,
+                       ( void* ) d_pred, pred_stride, ( const void* ) d_org, ( void* ) d_resi );
+  for( int p = 0; p < n_planes; p++ )
+    if( planes_host[p].d_base && ( planes_host[p].stride < 2 || ( planes_host[p].stride & 1 ) ) )
+      return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch: plane %d has stride %d (reference planes need an even row pitch in samples)", p, planes_host[p].stride );
+  if( n == 0 ) return VVHIP_OK;
+
+  // ---- a list that is run again (same items, same plane table) is launched at once: no sort, no upload, no allocation, no wait — such a call can be recorded in a launch graph
+  std::vector<unsigned char> key( sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ) + ( size_t ) n * sizeof( vvhip_pred_item ) );
+  memcpy( key.data(), &n_planes, sizeof( int ) );
+  memcpy( key.data() + sizeof( int ), planes_host, ( size_t ) n_planes * sizeof( vvhip_me_plane ) );
+  memcpy( key.data() + sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ), items_host, ( size_t ) n * sizeof( vvhip_pred_item ) );
+  if( key != ctx->predKey )
+  {
+    const int rc = predBuildSchedule( ctx, planes_host, n_planes, items_host, n, key );
+    if( rc ) return rc;
+  }
+  else if( ctx->predStream != ctx->stream )      // same schedule, other stream: order it behind the upload
+  {
+    if( ctx->predEventRecorded ) VVHIP_CHECK_HIP( ctx, hipStreamWaitEvent( ctx->stream, ctx->predEvent, 0 ) );
+    ctx->predStream = ctx->stream;
+  }
+  const size_t bItems = ctx->predOffSubs, bSubs = ctx->predOffUnits - ctx->predOffSubs;
+  const int ldsPerWave = ctx->predLdsPerWave, nUnits = ctx->predUnits;
+  PredArgs a;
+  const char* base = static_cast<const char*>( ctx->d_predSched );
+  a.items = reinterpret_cast<const PredDev*>( base ); a.subs = reinterpret_cast<const PredSub*>( base + bItems ); a.units = reinterpret_cast<const PredUnit*>( base + bItems + bSubs );
+  a.nUnits = nUnits; a.bitDepth = bit_depth; a.ldsPerWave = ldsPerWave;
+  a.pred = d_pred; a.predStride = pred_stride; a.org = d_resi ? d_org : nullptr; a.orgStride = org_stride; a.resi = d_resi;
+  hipLaunchKernelGGL( predListKernel, dim3( ( unsigned ) ( nUnits / 4 ) ), dim3( 256 ), ( size_t ) ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a );
+  VVHIP_LAUNCH_CHECK( ctx );
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if( hipStreamIsCapturing( ctx->stream, &cap ) != hipSuccess ) cap = hipStreamCaptureStatusNone;
+  if( cap == hipStreamCaptureStatusNone )      // (a launch recorded into a graph runs later: the graph's owner keeps the list unchanged while the graph is in use)
+  {
+    if( !ctx->predEvent ) VVHIP_CHECK_HIP( ctx, hipEventCreateWithFlags( &ctx->predEvent, hipEventDisableTiming ) );
+    VVHIP_CHECK_HIP( ctx, hipEventRecord( ctx->predEvent, ctx->stream ) );
+    ctx->predEventRecorded = true;
+  }
+  return VVHIP_OK;
+}
+
+int vvhip_interp_chroma_batch( vvhip_ctx* ctx, const int16_t* d_ref, int ref_stride, const vvhip_subpel_item* d_items, int n,
+                               int width, int height, int bit_depth, int rnd_res, int16_t* d_out )
+{
+  if( !ctx ) return VVHIP_E_ARG;
+  if( !isPow2( width ) || !isPow2( height ) || width < 2 || height < 2 || width > 64 || height > 64 || bit_depth < 8 || bit_depth > 12 || n < 0 || ref_stride < 2 || ( ref_stride & 1 ) ||
+      ( n && ( !d_ref || !d_items || !d_out ) ) )
+    return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_interp_chroma_batch: block %dx%d (powers of two, 2..64) bitDepth %d stride %d (even)", width, height, bit_depth, ref_stride );
+  if( n == 0 ) return VVHIP_OK;
+  const TileShape ts = tileShape( width, height, true );
+  const int subsPerWave = 64 >> ts.log2Lanes, ldsPerWave = subsPerWave * subElems( ts.tw, ts.th, 4 );
+  const long long tiles = ( long long ) n * ( width / ts.tw ) * ( height / ts.th ), waves = ( tiles + subsPerWave - 1 ) / subsPerWave;
+  hipLaunchKernelGGL( predOneSizeKernel, dim3( ( unsigned ) ( ( waves + 3 ) / 4 ) ), dim3( 256 ), ( size_t ) ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, d_ref, ref_stride, d_items, n,
+                      width, height, bit_depth, rnd_res ? 1 : 0, ts.kind, ts.tw, ts.th, ts.log2SegsRow, ts.log2Lanes, ldsPerWave, d_out );
+  VVHIP_LAUNCH_CHECK( ctx );
+  return VVHIP_OK;
+}
+
+} // extern "C"

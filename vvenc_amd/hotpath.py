@@ -23,6 +23,8 @@ MV_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("error", "<i4"), ("rmsme", "<i
 DMVR_ITEM_DTYPE = np.dtype([("ref0_off", "<i4"), ("ref1_off", "<i4"), ("frac0_x", "<i2"), ("frac0_y", "<i2"), ("frac1_x", "<i2"), ("frac1_y", "<i2")])
 DMVR_RESULT_DTYPE = np.dtype([("mvd_x", "<i2"), ("mvd_y", "<i2"), ("pad", "<i4"), ("min_cost", "<u8")])
 SUBPEL_DTYPE = np.dtype([("org_off", "<i4"), ("ref_off", "<i4"), ("frac_x", "<i2"), ("frac_y", "<i2")])
+PRED_ITEM_DTYPE = np.dtype([("dst_off", "<i4"), ("org_off", "<i4"), ("ref_off", "<i4", (2,)), ("frac", "<i2", (2, 2)), ("width", "<i2"), ("height", "<i2"),
+                            ("ref_plane", "i1", (2,)), ("chroma", "u1"), ("alt_hpel", "u1")])      # vvhip_pred_item (32 bytes)
 STATS_DTYPE = np.dtype([("abs_sum", "<i4"), ("last_scan_pos", "<i4"), ("need_rdoq", "<i4"), ("pad", "<i4"), ("sse", "<u8")])
 
 
@@ -510,6 +512,26 @@ class HotPath:
         self._ck(self.L.vvhip_interp_luma_batch(self.ctx, ref.buf_ptr, ref.stride, _ptr(d_items), n, w, h, bit_depth, int(rnd_res), filter_mode,
                                                 int(use_alt_hpel), _ptr(out)))
         return out
+
+    def interp_chroma_batch(self, ref, d_items, n, w, h, bit_depth=10, rnd_res=True, out=None):
+        """4:2:0 chroma prediction blocks of one size at 1/32-sample vectors (d_items: SUBPEL_DTYPE records) -> (n, h, w) int16; rnd_res False: the 14-bit intermediate"""
+        if out is None:
+            out = torch.empty(n * w * h, dtype=torch.int16, device=self.device)
+        self._ck(self.L.vvhip_interp_chroma_batch(self.ctx, ref.buf_ptr, ref.stride, _ptr(d_items), n, w, h, bit_depth, int(rnd_res), _ptr(out)))
+        return out
+
+    class _MePlane(C.Structure):          # vvhip_me_plane
+        _fields_ = [("d_base", C.c_void_p), ("stride", C.c_int32), ("reserved", C.c_int32)]
+
+    def pred_inter_batch(self, planes, items, pred, pred_stride=0, bit_depth=10, org=None, resi=None):
+        """inter prediction of a list of prediction units in one launch: planes = the reference Planes the items' ref_plane indexes, items = PRED_ITEM_DTYPE records
+        (HOST array: the library sorts it into size classes), pred = int16 tensor (compact blocks at dst_off, or a plane of row pitch pred_stride).
+        org (a Plane) + resi (int16 tensor laid out like pred): also writes org - pred."""
+        it = np.ascontiguousarray(items, PRED_ITEM_DTYPE)
+        tab = (self._MePlane * max(1, len(planes)))(*[self._MePlane(p.buf_ptr.value, p.stride, 0) for p in planes])
+        self._ck(self.L.vvhip_pred_inter_batch(self.ctx, C.cast(tab, C.c_void_p), len(planes), it.ctypes.data_as(C.c_void_p) if it.size else None, int(it.size), bit_depth,
+                                               _ptr(pred), pred_stride, org.buf_ptr if org is not None else None, org.stride if org is not None else 0, _ptr(resi)))
+        return pred
 
     def subpel_dist_batch(self, func, org, ref, d_items, n, w, h, bit_depth=10, filter_mode=0, use_alt_hpel=False, out=None):
         """distortion of sub-pel candidates: interpolate at the fractional vector, score against the original block"""
