@@ -439,9 +439,10 @@ VVHIP_API int  vvhip_me_plan_info( const vvhip_me_plan* plan, int* waves_int, in
  * fetched as aligned dwords), and needs an even row pitch; a zero fraction reads no rows above / below the block.
  * Unsupported input (a size that is not a power of two or out of range, a plane index outside the table, both lists unused, a fraction out of range) returns VVHIP_E_ARG with a
  * message before anything is launched.
- * NOT done here (the caller's job, as before): BDOF; the padded-reference rule of DMVR (DMVR::xFinalPaddedMCForDMVR, CommonLib/InterPrediction.cpp:1189-1260: a refined
- * sub-block's final prediction reads a padded copy of its PREFETCHED window, not the true plane — this entry is exact for DMVR sub-blocks whose refinement is zero and for every
- * non-DMVR PU); BCW and explicit weighted prediction; GEO blending; affine / PROF; IBC; reference picture resampling; the chroma phases of 4:2:2 and 4:4:4.
+ * BDOF and the padded-reference rule of DMVR (DMVR::xFinalPaddedMCForDMVR, CommonLib/InterPrediction.cpp:1189-1225: a refined sub-block's final prediction reads a padded
+ * copy of its PREFETCHED window, not the true plane) are per-item extensions: vvhip_pred_inter_batch_ex below.  Without them this entry is exact for DMVR sub-blocks whose
+ * refinement is zero and for every PU BDOF does not apply to.
+ * NOT done here (the caller's job, as before): BCW and explicit weighted prediction; GEO blending; affine / PROF; IBC; reference picture resampling; the chroma phases of 4:2:2 and 4:4:4.
  * ====================================================================================================================== */
 typedef struct
 {
@@ -458,6 +459,35 @@ VVHIP_API int vvhip_pred_inter_batch( vvhip_ctx* ctx, const vvhip_me_plane* plan
                                       const vvhip_pred_item* items_host, int n, int bit_depth,
                                       int16_t* d_pred, int pred_stride,
                                       const int16_t* d_org /* may be NULL */, int org_stride, int16_t* d_resi /* may be NULL */ );
+/* The same entry with a per-item extension (ext_host: a HOST array parallel to items_host; NULL = exactly vvhip_pred_inter_batch):
+ *   VVHIP_PRED_EXT_BDOF     : bi-directional optical flow on a true bi-predicted luma block (InterPrediction.cpp:465-490, xSubPuBDOF :326-357, xPredInterBlk :822-831 +
+ *               :868-901, xApplyBDOF :911-958, gradFilterCore :114-155, calcBDOFSumsCore :157-186, xFpBiDirOptFlowCore :607-661, addBDOFAvgCore :63-86).  Any luma size
+ *               8..128 with min( w, h ) >= 8 and w * h >= 128; the library cuts the block into the 16x16 / 16x8 / 8x16 units the reference predicts on their own (each
+ *               with its own one-sample ring of integer samples and its own replication padding).  The conditions on POC distances and CU flags (SMVD, BCW, CIIP, affine)
+ *               are the caller's; the chroma blocks of such a PU are plain bi-predicted items.
+ *   VVHIP_PRED_EXT_DMVR_PAD : the padded-reference rule of DMVR's final motion compensation (xCopyAndPad :1088-1130, xFinalPaddedMCForDMVR :1189-1225) for one refined
+ *               sub-block (<= 16x16 luma, its chroma blocks likewise).  ref_off[l] / frac[l] describe the REFINED vector; pad_dx / pad_dy[l] = refined_int - start_int
+ *               per list (|.| <= 2 luma, <= 1 chroma), so ref_off[l] - ( pad_dy[l] * stride + pad_dx[l] ) is the start position.  Every sample the block reads (the BDOF
+ *               ring included) has its coordinates clamped to the window prefetched around the start vector: ( w + T - 1 ) x ( h + T - 1 ) samples from
+ *               start - ( T / 2 - 1 ), T = 8 luma / 4 chroma — what reading the replication-padded copy gives.  A zero delta reads the true plane.
+ *               With both flags the item is one BDOF unit (<= 16x16); the caller sets the BDOF flag per sub-block as its own flag AND min_cost >= 2 * dx * dy (:1307, :1384).
+ * Argument errors (VVHIP_E_ARG with a message, nothing launched): BDOF on chroma, with one list or on a size that fails the rule; a delta out of range; unknown flag bits or
+ * non-zero reserved bytes.  Everything vvhip_pred_inter_batch promises holds: order independence, the schedule cache (the extension array is part of the list's key),
+ * the residual, both output layouts.  Margins: the BDOF ring lies one sample beyond the block, inside the 4-sample luma margin; a DMVR item reads inside the margin
+ * of its START position.                                                                                                                                                  */
+#define VVHIP_PRED_EXT_BDOF     1
+#define VVHIP_PRED_EXT_DMVR_PAD 2
+typedef struct
+{
+  uint8_t flags;              /* VVHIP_PRED_EXT_*                                                                      */
+  int8_t  pad_dx[2];          /* per list: refined_int - start_int, x (DMVR_PAD only)                                  */
+  int8_t  pad_dy[2];          /* per list: refined_int - start_int, y                                                  */
+  uint8_t rsv[3];             /* zero                                                                                  */
+} vvhip_pred_ext;             /* 8 bytes */
+VVHIP_API int vvhip_pred_inter_batch_ex( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host,
+                                         const vvhip_pred_ext* ext_host /* may be NULL */, int n, int bit_depth,
+                                         int16_t* d_pred, int pred_stride,
+                                         const int16_t* d_org /* may be NULL */, int org_stride, int16_t* d_resi /* may be NULL */ );
 /* The chroma twin of vvhip_interp_luma_batch: n blocks of ONE size (powers of two, 2..64) from one plane, items on the device (frac_x / frac_y in 1/32 sample, org_off unused),
  * compact output d_out[i*w*h + y*w + x]; rnd_res 1 = final samples, 0 = the 14-bit intermediate a bi-prediction average consumes.  Margins as above.                            */
 VVHIP_API int vvhip_interp_chroma_batch( vvhip_ctx* ctx, const int16_t* d_ref, int ref_stride, const vvhip_subpel_item* d_items, int n,
@@ -577,8 +607,8 @@ VVHIP_API int vvhip_mctf_filter_params( int qp, int bit_depth, double overall_st
  *   ref0_off / ref1_off : the sub-block's integer position for the merge vector of list 0 / 1 (mv >> 4), frac* = mv & 15
  *   result              : mvd = cu.mvdL0SubPu[num] in 1/16 sample (list 1 moves by -mvd), min_cost = the value the BDOF switch compares
  *                         with 2*dx*dy (:1386).  The final motion compensation: sub-blocks whose refinement is zero go into a prediction list
- *                         (vvhip_pred_inter_batch: luma + chroma, both lists, the average); a refined sub-block needs DMVR's padded-reference rule
- *                         (xFinalPaddedMCForDMVR, :1189-1260) and BDOF, which stay with the caller.                                          */
+ *                         (vvhip_pred_inter_batch: luma + chroma, both lists, the average); a refined sub-block reads through DMVR's padded-reference
+ *                         rule (xFinalPaddedMCForDMVR, :1189-1225), with BDOF where min_cost allows it: vvhip_pred_inter_batch_ex.            */
 typedef struct { int32_t ref0_off, ref1_off; int16_t frac0_x, frac0_y, frac1_x, frac1_y; } vvhip_dmvr_item;
 typedef struct { int16_t mvd_x, mvd_y; int32_t pad; uint64_t min_cost; } vvhip_dmvr_result;
 VVHIP_API int vvhip_dmvr_refine_batch( vvhip_ctx* ctx, const int16_t* d_ref0, int stride0, const int16_t* d_ref1, int stride1,

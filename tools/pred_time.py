@@ -10,7 +10,7 @@ B. the realistic list: a B picture's mix of prediction units — the fixed histo
    lists, most samples in 64x64 and 32x32 units, most units 16x16 and smaller), half of the units bi-predicted (seeded), luma + both 4:2:0 chroma blocks per unit, residual
    output on.  Reported: time per picture, the bytes the algorithm reads and writes (per list the window (w + taps - 1) x (h + taps - 1), the original block, prediction and
    residual blocks; 2 bytes per sample) and their fraction of the HBM peak, the host time of a first call (sort + schedule + upload) and of a repeated call (the list is
-   recognised).
+   recognised).  The same list again with BDOF set on its true bi-predicted luma items that pass BDOF's size rule (vvhip_pred_inter_batch_ex), in the same rounds.
 Every variant is recorded into a launch graph once and timed as `reps` graph launches between two host clock readings that end in a device synchronise, `rounds` times, the
 variants alternating inside a round; medians, minima and the spread ( max - min ) / median are printed.  --quick: one round of few launches (for a profiler run)."""
 import argparse
@@ -209,13 +209,40 @@ def main():
     hp.sync()
     g_mix = hp.graph_capture(mix_fn)
     variants["b_picture"] = g_mix
-    run("b_picture", 5)
-    tm = [run("b_picture", a.reps) for _ in range(a.rounds)]
-    st = stats(tm)
+    # the same list with BDOF on every true bi-predicted luma item the size rule admits (a second context: each context caches the schedule of ONE list)
+    from vvenc_amd.hotpath import PRED_EXT_BDOF, PRED_EXT_DTYPE
+    ext = np.zeros(len(items), PRED_EXT_DTYPE)
+    on = (items["chroma"] == 0) & (items["ref_plane"][:, 0] >= 0) & (items["ref_plane"][:, 1] >= 0) & (np.minimum(items["width"], items["height"]) >= 8) & \
+         (items["width"].astype(np.int32) * items["height"] >= 128)
+    ext["flags"][on] = PRED_EXT_BDOF
+    hp2 = HotPath()
+    hp2.use_own_stream()
+    pred2 = torch.zeros(total, dtype=torch.int16, device=hp.device)
+    resi2 = torch.zeros(total, dtype=torch.int16, device=hp.device)
+    bdof_fn = lambda: hp2.pred_inter_batch(table, items, pred2, 0, 10, org, resi2, ext=ext)
+    bdof_fn(); hp2.sync()
+    g_bdof = hp2.graph_capture(bdof_fn)
+
+    def run_bdof(reps):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            hp2.graph_launch(g_bdof)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps
+    run("b_picture", 5); run_bdof(5)
+    tm, tb = [], []
+    for r in range(a.rounds):
+        if r % 2 == 0:
+            tm.append(run("b_picture", a.reps)); tb.append(run_bdof(a.reps))
+        else:
+            tb.append(run_bdof(a.reps)); tm.append(run("b_picture", a.reps))
+    st, sb = stats(tm), stats(tb)
     sec = st["median_us"] * 1e-6
     res["b_picture_mix"] = {"units": int(sum(PU_HIST.values())), "items": int(len(items)), "bi_items": int(((items["ref_plane"][:, 0] >= 0) & (items["ref_plane"][:, 1] >= 0)).sum()),
                             "samples": int(total), **st, "bytes_read": int(rd), "bytes_written": int(wr), "achieved_GBps": round((rd + wr) / sec / 1e9, 1),
                             "hbm_peak_fraction": round((rd + wr) / sec / HBM_PEAK, 4), "host_first_call_us": round(host_first * 1e6, 1), "host_repeated_call_us": round(host_again * 1e6, 1)}
+    res["b_picture_mix_bdof"] = {"items": int(len(items)), "bdof_items": int(on.sum()), "bdof_samples": int((items["width"].astype(np.int64) * items["height"])[on].sum()), **sb,
+                                 "ratio_to_plain": round(sb["median_us"] / st["median_us"], 3), "changed_samples": int((pred2 != pred).sum().item())}
     for k, v in res.items():
         print(k, json.dumps(v) if isinstance(v, dict) else v)
     if a.json:

@@ -47,6 +47,7 @@ struct vvhip_ctx
   std::vector<unsigned char> predKey, predBlob;
   size_t       predOffSubs = 0, predOffUnits = 0;
   int          predUnits  = 0, predLdsPerWave = 0;
+  int          predUnitsEx = 0, predLdsPerWaveEx = 0;      // the units of items with an extension (BDOF, DMVR's padded reference): behind the plain units, a kernel of their own
   hipStream_t  predStream = nullptr;       // the stream the schedule was uploaded on; compared only, never used as a handle
   hipEvent_t   predEvent  = nullptr;       // recorded behind every launch that reads the schedule
   bool         predEventRecorded = false;

@@ -221,8 +221,8 @@ struct QuantOps
 
 // DMVR refinement search of one CU in one device call (DMVR::xProcessDMVR, CommonLib/InterPrediction.cpp:1262-1392).
 // What to do with the result: sub-blocks whose refinement is zero (and every PU that is not refined at all) can go straight into a prediction list
-// (InterPredOps::predictList: luma and chroma, both lists, the average); a sub-block with a non-zero refinement needs DMVR's padded-reference rule for its final
-// prediction (DMVR::xFinalPaddedMCForDMVR, :1189-1260) and BDOF where the cost switch leaves it on — both stay with the caller.
+// (InterPredOps::predictList: luma and chroma, both lists, the average); a sub-block with a non-zero refinement goes into the same list with an extension record
+// (vvhip_pred_ext): DMVR's padded-reference rule for its final prediction (DMVR::xFinalPaddedMCForDMVR, :1189-1225), and BDOF where the cost switch leaves it on.
 struct DMVROps
 {
   // ref0 / ref1: the reference samples at the CU's position displaced by the integer part of the (clipped) merge vectors MINUS 2 samples in
@@ -241,7 +241,10 @@ struct InterPredOps
   // block's place in the compact outputs (row pitch = width).  pred: predElems samples.  org (may be nullptr; a registered picture like the references) + resi: also
   // org - pred, laid out like pred; org_off at the picture's line pitch.  false: a plane is not registered on this GPU (nothing was run).  Throws like every table entry when
   // the device rejects the list (vvhip::Exception with the entry's message).
-  bool predictList( const Pel* const* refPlanes, int numPlanes, const vvhip_pred_item* items, int n, int bitDepth, Pel* pred, size_t predElems, const Pel* org = nullptr, Pel* resi = nullptr );
+  // ext (may be nullptr): vvhip_pred_ext records parallel to items — BDOF on true bi-predicted luma blocks, DMVR's padded reference for refined sub-blocks
+  // (vvhip_pred_inter_batch_ex).
+  bool predictList( const Pel* const* refPlanes, int numPlanes, const vvhip_pred_item* items, int n, int bitDepth, Pel* pred, size_t predElems, const Pel* org = nullptr, Pel* resi = nullptr,
+                    const vvhip_pred_ext* ext = nullptr );
 };
 
 // ALF encoder statistics: whole-plane forms of AdaptiveLoopFilter::m_deriveClassificationBlk (CommonLib/AdaptiveLoopFilter.h,

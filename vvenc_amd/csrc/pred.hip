@@ -15,6 +15,13 @@
 // vector with one zero fraction (floor( ( floor( a / 4 ) + b ) / c ) = floor( ( a + 4 b ) / ( 4 c ) ) for integers — the rule interp.hip's refinement kernel already relies on).
 // A bi-predicted block keeps list 0's 14-bit block in registers while list 1 goes through the same LDS, then averages: the two intermediates never leave the wave.
 // Waves synchronise with themselves only (no workgroup barrier); a workgroup is four independent waves.
+//
+// Items with an extension record (vvhip_pred_inter_batch_ex) run in predListExKernel, the same body with two additions:
+//   DMVR's padded reference   DMVR::xCopyAndPad :1088-1130, xFinalPaddedMCForDMVR :1189-1225: step 1 clamps every sample's coordinates to the window prefetched round the START vector.
+//   BDOF                      xSubPuBDOF :326-357, xPredInterBlk :822-831 + :868-901, xApplyBDOF :911-958, gradFilterCore :114-155, calcBDOFSumsCore :157-186,
+//                             xFpBiDirOptFlowCore :607-661, addBDOFAvgCore :63-86: a lane group per 16x16 / 16x8 / 8x16 unit; each list's 14-bit block goes to LDS inside its ring
+//                             of integer samples, the lanes take the gradients of their own samples, a lane pair per 4x4 unit sums the 6x6 window, the offsets come back by lane read.
+// Still the caller's: the BDOF conditions on POC distances and CU flags, BCW / explicit weighted prediction, GEO, affine / PROF.
 #include <algorithm>
 #include <string.h>
 #include "common.h"
@@ -41,10 +48,10 @@ struct __attribute__( ( aligned( 16 ) ) ) PredDev      // one prediction item wi
   int32_t dstOff, orgOff;
   int16_t frac[2][2];
   int16_t w, h;
-  uint8_t alt, pad[3];
+  uint8_t alt, pad[3];           // extension forms: pad[0] = flags, pad[1 + l] = ( pad_dx[l] + 2 ) | ( pad_dy[l] + 2 ) << 4
 };
 struct PredSub  { int32_t item; int16_t x0, y0; };      // one tile of an item
-struct PredUnit { int32_t firstSub; int16_t nSub, tw, th; uint8_t kind, log2Lanes, log2SegsRow, pad[3]; };      // what one wave does
+struct PredUnit { int32_t firstSub; int16_t nSub, tw, th; uint8_t kind, log2Lanes, log2SegsRow, pad[3]; };      // what one wave does (pad[0]: the extension flags of its class)
 static_assert( sizeof( PredDev ) == 48 && sizeof( PredSub ) == 8 && sizeof( PredUnit ) == 16, "schedule records" );
 
 // kernel forms: samples per lane (a "segment": SEG horizontally adjacent samples) x taps per pass
@@ -85,6 +92,10 @@ struct Lane
   int16_t* dst; int dstPitch;    // block origin in the prediction buffer
   const int16_t* org; int orgPitch;
   int16_t* res; int resPitch;    // null: no residual
+  // extension forms only (predBody<.., true>): BDOF unit, DMVR clamp window per list in block coordinates (inclusive), BDOF arrays
+  bool bdof, clamp;
+  int cx0[2], cx1[2], cy0[2], cy1[2];
+  int16_t* ext;
 };
 
 #define PRED_WAVE_SYNC() { __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" ); __builtin_amdgcn_wave_barrier(); }
@@ -119,7 +130,14 @@ __device__ __forceinline__ void loadTaps( int ( &c )[NT], int& lo, int frac, boo
 
 template<int SEG> struct __attribute__( ( aligned( SEG * 2 ) ) ) SegRow { int16_t v[SEG]; };
 
-template<int SEG, int NT>
+// LDS samples a BDOF unit keeps beside its window: list 0's 14-bit block with its one-sample ring, then ( gx0 + gx1 ) >> 1, ( gy0 + gy1 ) >> 1, ( s1 >> 4 ) - ( s0 >> 4 )
+__host__ __device__ inline int bdofRingElems( int tw, int th ) { return ( ( tw + 2 ) * ( th + 2 ) + 7 ) & ~7; }
+__host__ __device__ inline int bdofElems( int tw, int th ) { return bdofRingElems( tw, th ) + 3 * tw * th; }
+
+__device__ __forceinline__ int clampi( int v, int lo, int hi ) { return v < lo ? lo : ( v > hi ? hi : v ); }
+
+// EX = false: the forms of vvhip_pred_inter_batch.  EX = true adds, per unit of the schedule, the DMVR clamp in the window staging and the BDOF form of the average.
+template<int SEG, int NT, bool EX = false>
 __device__ __forceinline__ void predBody( const Lane& L, int tw, int th, int log2SegsRow, int lanes, int bitDepth )
 {
   constexpr int ND = ( SEG + NT ) / 2 + 1;              // dwords that hold a segment's SEG + NT - 1 window samples at either alignment
@@ -151,6 +169,23 @@ __device__ __forceinline__ void predBody( const Lane& L, int tw, int th, int log
       const int dwRow = ( cols + sh + 1 ) >> 1, strideDw = L.stride[l] >> 1;        // (the stride is even: every row has the same alignment)
       uint32_t* w32 = reinterpret_cast<uint32_t*>( L.win );
       const int l2 = 32 - __builtin_clz( ( unsigned ) ( dwRow - 1 ) | 1u );      // rows are dealt in strides of the next power of two: no division (a quarter of the slots idle at worst)
+      if( EX && L.clamp )
+      {
+        // DMVR's final motion compensation reads a replication-padded copy of the window prefetched around the START vector (xCopyAndPad, xFinalPaddedMCForDMVR):
+        // the same dword slots, every sample's coordinates clamped to that window
+        for( int i = L.lis; i < ( rows << l2 ); i += lanes )
+        {
+          const int r = i >> l2, d = i & ( ( 1 << l2 ) - 1 );
+          if( d < dwRow )
+          {
+            const int yy = clampi( L.y0 - loY + r, L.cy0[l], L.cy1[l] ), xx = L.x0 - loX - sh + 2 * d;
+            const int16_t* row = L.ref[l] + ( ptrdiff_t ) yy * L.stride[l];
+            const uint32_t lo16 = ( uint16_t ) row[clampi( xx, L.cx0[l], L.cx1[l] )], hi16 = ( uint16_t ) row[clampi( xx + 1, L.cx0[l], L.cx1[l] )];
+            w32[r * ( pitch >> 1 ) + d] = lo16 | ( hi16 << 16 );
+          }
+        }
+      }
+      else
       for( int i = L.lis; i < ( rows << l2 ); i += lanes )
       {
         const int r = i >> l2, d = i & ( ( 1 << l2 ) - 1 );
@@ -219,9 +254,107 @@ __device__ __forceinline__ void predBody( const Lane& L, int tw, int th, int log
 #pragma unroll
       for( int j = 0; j < SEG; j++ ) first[j] = acc[j];
     }
+    if( EX && SEG == 8 && NT == 8 )
+    {
+      // ---- BDOF: the list's 14-bit block inside a one-sample ring of integer samples at the nearest-integer position, ( ref << headroom ) - IF_INTERNAL_OFFS
+      //      (xPredInterBlk :868-901).  List 0 keeps its frame beside the window; list 1's frame reuses the window, which nobody reads any more.
+      if( L.bdof && use )
+      {
+        const int pp = tw + 2;
+        int16_t* P = l == 0 ? L.ext : L.win;
+#pragma unroll
+        for( int j = 0; j < SEG; j++ ) P[( y + 1 ) * pp + xs + 1 + j] = ( int16_t ) acc[j];
+        const int xo = L.fx[l] < 8 ? 1 : 0, yo = L.fy[l] < 8 ? 1 : 0, nRing = 2 * pp + 2 * th;
+        for( int i = L.lis; i < nRing; i += lanes )
+        {
+          int fx, fy;
+          if( i < 2 * pp ) { fy = i < pp ? 0 : th + 1; fx = i < pp ? i : i - pp; }
+          else { const int k = i - 2 * pp; fy = 1 + ( k >> 1 ); fx = ( k & 1 ) ? tw + 1 : 0; }
+          int cx = L.x0 + fx - xo, cy = L.y0 + fy - yo;
+          if( L.clamp ) { cx = clampi( cx, L.cx0[l], L.cx1[l] ); cy = clampi( cy, L.cy0[l], L.cy1[l] ); }
+          P[fy * pp + fx] = ( int16_t ) ( ( ( int ) L.ref[l][( ptrdiff_t ) cy * L.stride[l] + cx] << hr ) - 8192 );
+        }
+      }
+      if( L.bdof ) PRED_WAVE_SYNC();
+    }
+  }
+  if( EX && SEG == 8 && NT == 8 )
+  {
+    if( L.bdof )      // (uniform over the wave: a unit of the schedule holds one form)
+    {
+      // ---- gradients of both lists on the lane's own samples, the ring as neighbours (gradFilterCore :114-131)
+      const int pp = tw + 2;
+      int dgx[SEG], dgy[SEG];
+      SegRow<SEG> tgx, tgy, tdi;
+      {
+        int gx[2][SEG], gy[2][SEG];
+#pragma unroll
+        for( int l = 0; l < 2; l++ )
+        {
+          const int16_t* P = ( l == 0 ? L.ext : L.win ) + ( y + 1 ) * pp + xs + 1;
+          int c[SEG + 2];
+#pragma unroll
+          for( int j = 0; j < SEG + 2; j++ ) c[j] = ( int ) P[j - 1] >> 6;
+#pragma unroll
+          for( int j = 0; j < SEG; j++ ) { gx[l][j] = c[j + 2] - c[j]; gy[l][j] = ( ( int ) P[j + pp] >> 6 ) - ( ( int ) P[j - pp] >> 6 ); }
+        }
+#pragma unroll
+        for( int j = 0; j < SEG; j++ )
+        {
+          dgx[j] = gx[0][j] - gx[1][j]; dgy[j] = gy[0][j] - gy[1][j];
+          tgx.v[j] = ( int16_t ) ( ( gx[0][j] + gx[1][j] ) >> 1 ); tgy.v[j] = ( int16_t ) ( ( gy[0][j] + gy[1][j] ) >> 1 );
+          tdi.v[j] = ( int16_t ) ( ( acc[j] >> 4 ) - ( first[j] >> 4 ) );
+        }
+      }
+      // the window sums read the replication-padded arrays (gradFilterCore :133-154, xApplyBDOF :939-949): the interior at clamped coordinates
+      int16_t* tGX = L.ext + bdofRingElems( tw, th );
+      int16_t* tGY = tGX + tw * th;
+      int16_t* tDI = tGY + tw * th;
+      *reinterpret_cast<SegRow<SEG>*>( tGX + y * tw + xs ) = tgx;
+      *reinterpret_cast<SegRow<SEG>*>( tGY + y * tw + xs ) = tgy;
+      *reinterpret_cast<SegRow<SEG>*>( tDI + y * tw + xs ) = tdi;
+      PRED_WAVE_SYNC();
+      // ---- a lane pair per 4x4 unit, three rows of its 6x6 window each (calcBDOFSumsCore :157-186); the group has exactly two lanes per unit
+      const int u = L.lis >> 1, half = L.lis & 1, l2u = log2SegsRow + 1;
+      const int uy = u >> l2u, ux = u & ( ( 1 << l2u ) - 1 );
+      int sAbsGX = 0, sAbsGY = 0, sDIX = 0, sDIY = 0, sSign = 0;
+#pragma unroll
+      for( int r = 0; r < 3; r++ )
+      {
+        const int yy = clampi( 4 * uy - 1 + 3 * half + r, 0, th - 1 ) * tw;
+#pragma unroll
+        for( int cidx = 0; cidx < 6; cidx++ )
+        {
+          const int o = yy + clampi( 4 * ux - 1 + cidx, 0, tw - 1 );
+          const int g = tGX[o], v = tGY[o], d = tDI[o];
+          sAbsGX += g < 0 ? -g : g; sAbsGY += v < 0 ? -v : v;
+          sDIX += g < 0 ? -d : ( g == 0 ? 0 : d );
+          sDIY += v < 0 ? -d : ( v == 0 ? 0 : d );
+          sSign += v < 0 ? -g : ( v == 0 ? 0 : g );
+        }
+      }
+      sAbsGX += __shfl_xor( sAbsGX, 1 ); sAbsGY += __shfl_xor( sAbsGY, 1 ); sDIX += __shfl_xor( sDIX, 1 ); sDIY += __shfl_xor( sDIY, 1 ); sSign += __shfl_xor( sSign, 1 );
+      // the two offsets (xFpBiDirOptFlowCore :642-647): floorLog2 = 31 - clz
+      int tmpx = sAbsGX ? clampi( ( 4 * sDIX ) >> ( 31 - __builtin_clz( ( unsigned ) sAbsGX ) ), -15, 15 ) : 0;
+      int tmpy = sAbsGY ? clampi( ( 4 * sDIY - ( ( sSign * tmpx ) >> 1 ) ) >> ( 31 - __builtin_clz( ( unsigned ) sAbsGY ) ), -15, 15 ) : 0;
+      const int packed = ( tmpx & 0xffff ) | ( tmpy << 16 );
+      const int base = ( int ) ( threadIdx.x & 63 ) - L.lis, ua = ( ( y >> 2 ) << l2u ) + ( xs >> 2 );
+      const int pa = __shfl( packed, base + 2 * ua ), pb = __shfl( packed, base + 2 * ua + 2 );
+      // ---- addBDOFAvgCore :63-86: ClipPel( (int16_t) ( ( s0 + s1 + b + offset ) >> shiftNum ) ), shiftNum = 15 - bitDepth
+      const int sn = 15 - bitDepth, off = ( 1 << ( sn - 1 ) ) + 2 * 8192;
+#pragma unroll
+      for( int j = 0; j < SEG; j++ )
+      {
+        const int pk = j < 4 ? pa : pb, tx = ( int ) ( int16_t ) ( pk & 0xffff ), ty = pk >> 16;
+        const int b = tx * dgx[j] + ty * dgy[j];
+        const int v = ( int16_t ) ( ( first[j] + acc[j] + b + off ) >> sn );
+        acc[j] = v < 0 ? 0 : ( v > maxv ? maxv : v );
+      }
+    }
   }
   if( !L.on ) return;
-  if( L.mode == MODE_BI )      // addAvg: ClipPel( ( a + b + offset ) >> shiftNum ), shiftNum = headroom + 1, offset = ( 1 << headroom ) + 2 * IF_INTERNAL_OFFS (Buffer.cpp:129-141, :549-575)
+  if( EX && SEG == 8 && NT == 8 && L.bdof ) {}
+  else if( L.mode == MODE_BI )      // addAvg: ClipPel( ( a + b + offset ) >> shiftNum ), shiftNum = headroom + 1, offset = ( 1 << headroom ) + 2 * IF_INTERNAL_OFFS (Buffer.cpp:129-141, :549-575)
   {
     const int sn = hr + 1, off = ( 1 << hr ) + 2 * 8192;
 #pragma unroll
@@ -277,6 +410,18 @@ __device__ __forceinline__ void predDispatch( int kind, const Lane& L, int tw, i
   }
 }
 
+__device__ __forceinline__ void predDispatchEx( int kind, const Lane& L, int tw, int th, int log2SegsRow, int lanes, int bitDepth )
+{
+  switch( kind )      // wave-uniform
+  {
+  case KIND_L8: predBody<8, 8, true>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_L4: predBody<4, 8, true>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_C8: predBody<8, 4, true>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_C4: predBody<4, 4, true>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  default:      predBody<2, 4, true>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  }
+}
+
 struct PredArgs
 {
   const PredDev* items; const PredSub* subs; const PredUnit* units;
@@ -314,6 +459,50 @@ predListKernel( PredArgs a )
   L.org = a.org ? a.org + it.orgOff : nullptr; L.orgPitch = a.orgStride;
   L.res = a.resi ? a.resi + it.dstOff : nullptr; L.resPitch = L.dstPitch;
   predDispatch( u.kind, L, u.tw, u.th, u.log2SegsRow, lanes, a.bitDepth );
+}
+
+// the units of items with an extension (vvhip_pred_inter_batch_ex): BDOF units (16x16 / 16x8 / 8x16, two or four per wave) and blocks read through DMVR's clamp window.
+// A kernel of its own: the forms of predListKernel keep their registers.
+__global__ void __launch_bounds__( 256 )
+predListExKernel( PredArgs a )
+{
+  extern __shared__ __attribute__( ( aligned( 16 ) ) ) int16_t sPred[];
+  const int wave = __builtin_amdgcn_readfirstlane( ( int ) ( threadIdx.x >> 6 ) ), lane = threadIdx.x & 63;
+  const int ui = ( int ) blockIdx.x * 4 + wave;
+  if( ui >= a.nUnits ) return;
+  const PredUnit u = a.units[ui];
+  if( u.nSub == 0 ) return;
+  const int nt = u.kind <= KIND_L4 ? 8 : 4, lanes = 1 << u.log2Lanes, si = lane >> u.log2Lanes;
+  Lane L;
+  L.bdof = ( u.pad[0] & VVHIP_PRED_EXT_BDOF ) != 0; L.clamp = ( u.pad[0] & VVHIP_PRED_EXT_DMVR_PAD ) != 0;
+  L.on = si < u.nSub;
+  L.lis = lane & ( lanes - 1 );
+  L.win = sPred + ( size_t ) wave * a.ldsPerWave + ( size_t ) si * ( subElems( u.tw, u.th, nt ) + ( L.bdof ? bdofElems( u.tw, u.th ) : 0 ) );
+  L.tmp = L.win + winElems( u.tw, u.th, nt );
+  L.ext = L.win + subElems( u.tw, u.th, nt );
+  const PredSub s = a.subs[u.firstSub + ( L.on ? si : 0 )];
+  const PredDev it = a.items[s.item];
+  L.ref[0] = it.ref[0]; L.ref[1] = it.ref[1]; L.stride[0] = it.stride[0]; L.stride[1] = it.stride[1];
+  L.fx[0] = it.frac[0][0]; L.fy[0] = it.frac[0][1]; L.fx[1] = it.frac[1][0]; L.fy[1] = it.frac[1][1];
+  L.w = it.w; L.h = it.h; L.alt = it.alt; L.x0 = s.x0; L.y0 = s.y0;
+  L.mode = it.ref[0] && it.ref[1] ? MODE_BI : MODE_UNI;
+  const int reach = nt / 2 - 1;      // the prefetched window: ( w + taps - 1 ) x ( h + taps - 1 ) samples from start - ( taps / 2 - 1 )
+#pragma unroll
+  for( int l = 0; l < 2; l++ )
+  {
+    const int pdx = ( it.pad[1 + l] & 15 ) - 2, pdy = ( it.pad[1 + l] >> 4 ) - 2;
+    L.cx0[l] = -reach - pdx; L.cx1[l] = it.w + reach - pdx; L.cy0[l] = -reach - pdy; L.cy1[l] = it.h + reach - pdy;
+  }
+  if( !it.ref[0] )      // a list-1-only block runs as the first pass
+  {
+    L.ref[0] = it.ref[1]; L.stride[0] = it.stride[1]; L.fx[0] = L.fx[1]; L.fy[0] = L.fy[1]; L.ref[1] = nullptr;
+    L.cx0[0] = L.cx0[1]; L.cx1[0] = L.cx1[1]; L.cy0[0] = L.cy0[1]; L.cy1[0] = L.cy1[1];
+  }
+  L.dstPitch = a.predStride ? a.predStride : it.w;
+  L.dst = a.pred + it.dstOff;
+  L.org = a.org ? a.org + it.orgOff : nullptr; L.orgPitch = a.orgStride;
+  L.res = a.resi ? a.resi + it.dstOff : nullptr; L.resPitch = L.dstPitch;
+  predDispatchEx( u.kind, L, u.tw, u.th, u.log2SegsRow, lanes, a.bitDepth );
 }
 
 // one block size per call, items on the device (the chroma twin of vvhip_interp_luma_batch): tile g of the launch is tile g % tilesPerItem of item g / tilesPerItem
@@ -362,7 +551,7 @@ std::vector<int> predBandOrder( int nGroups, int base )
 struct Keyed { uint32_t cls; int64_t pos; int idx; };
 
 // validates the list, derives the schedule and uploads it; on success the context's key names the list (items + plane table) the device copy belongs to
-int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, int n, std::vector<unsigned char>& key )
+int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host, int n, std::vector<unsigned char>& key )
 {
   // ---- validation + plane table resolved; nothing is launched when any item is unsupported
   std::vector<PredDev> dev( n );
@@ -389,9 +578,36 @@ int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_
       d.frac[l][0] = it.frac[l][0]; d.frac[l][1] = it.frac[l][1];
     }
     d.dstOff = it.dst_off; d.orgOff = it.org_off; d.w = it.width; d.h = it.height; d.alt = it.alt_hpel ? 1 : 0;
+    // ---- the extension: BDOF (luma, both lists, min( w, h ) >= 8 and w * h >= 128: InterPrediction.cpp:465-490) and DMVR's padded reference (|delta| <= DMVR_NUM_ITERATION >> scale)
+    uint32_t flags = 0;
+    if( ext_host )
+    {
+      const vvhip_pred_ext& e = ext_host[i];
+      if( ( e.flags & ~( VVHIP_PRED_EXT_BDOF | VVHIP_PRED_EXT_DMVR_PAD ) ) || e.rsv[0] || e.rsv[1] || e.rsv[2] )
+        return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ex: item %d: unknown flag bits or non-zero reserved bytes in the extension", i );
+      flags = e.flags;
+      if( flags & VVHIP_PRED_EXT_BDOF )
+      {
+        if( it.chroma ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ex: item %d: BDOF is a luma tool", i );
+        if( it.ref_plane[0] < 0 || it.ref_plane[1] < 0 ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ex: item %d: BDOF needs both reference lists", i );
+        if( std::min( it.width, it.height ) < 8 || it.width * it.height < 128 )
+          return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ex: item %d: BDOF on a %dx%d block (min( w, h ) >= 8 and w * h >= 128)", i, it.width, it.height );
+      }
+      if( flags & VVHIP_PRED_EXT_DMVR_PAD )
+      {
+        const int lim = it.chroma ? 1 : 2;
+        for( int l = 0; l < 2; l++ )
+          if( e.pad_dx[l] < -lim || e.pad_dx[l] > lim || e.pad_dy[l] < -lim || e.pad_dy[l] > lim )
+            return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ex: item %d: list %d integer delta (%d, %d) outside -%d..%d", i, l, e.pad_dx[l], e.pad_dy[l], lim, lim );
+        if( ( flags & VVHIP_PRED_EXT_BDOF ) && ( it.width > 16 || it.height > 16 ) )
+          return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ex: item %d: a DMVR sub-block with BDOF is at most 16x16, not %dx%d", i, it.width, it.height );
+        d.pad[1] = ( uint8_t ) ( ( e.pad_dx[0] + 2 ) | ( ( e.pad_dy[0] + 2 ) << 4 ) ); d.pad[2] = ( uint8_t ) ( ( e.pad_dx[1] + 2 ) | ( ( e.pad_dy[1] + 2 ) << 4 ) );
+      }
+      d.pad[0] = ( uint8_t ) flags;
+    }
     // size class: the most samples first (their waves run longest), then shape, component and uni / bi — a wave never mixes classes; inside a class picture order
     const bool bi = it.ref_plane[0] >= 0 && it.ref_plane[1] >= 0;
-    order[i].cls = ( ( uint32_t ) ( 14 - ilog2i( it.width ) - ilog2i( it.height ) ) << 8 ) | ( ( uint32_t ) ilog2i( it.width ) << 4 ) | ( it.chroma ? 2u : 0u ) | ( bi ? 1u : 0u );
+    order[i].cls = ( ( uint32_t ) ( 14 - ilog2i( it.width ) - ilog2i( it.height ) ) << 8 ) | ( ( uint32_t ) ilog2i( it.width ) << 4 ) | ( flags << 2 ) | ( it.chroma ? 2u : 0u ) | ( bi ? 1u : 0u );
     const int l0 = it.ref_plane[0] >= 0 ? 0 : 1;
     order[i].pos = ( ( int64_t ) it.ref_off[l0] << 5 ) | ( uint32_t ) ( it.ref_plane[l0] & 31 );
     order[i].idx = i;
@@ -399,16 +615,25 @@ int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_
   std::sort( order.begin(), order.end(), []( const Keyed& a, const Keyed& b ) { return a.cls != b.cls ? a.cls < b.cls : a.pos != b.pos ? a.pos < b.pos : a.idx < b.idx; } );
 
   // ---- schedule: per class the tiles in picture order, 64 lanes' worth per wave, four waves per workgroup, workgroups dealt to the XCDs in bands
+  //      classes with an extension flag go to a list of their own, which predListExKernel runs; a BDOF block is cut into its 16x16 / 16x8 / 8x16 units (xSubPuBDOF :326-357)
   std::vector<PredSub> subs;
-  std::vector<PredUnit> units;
-  int ldsPerWave = 0;
+  std::vector<PredUnit> unitsPlain, unitsEx;
+  int ldsPerWave = 0, ldsPerWaveEx = 0;
   for( int c0 = 0; c0 < n; )
   {
     int c1 = c0; while( c1 < n && order[c1].cls == order[c0].cls ) c1++;
     const vvhip_pred_item& f = items_host[order[c0].idx];
-    const TileShape ts = tileShape( f.width, f.height, f.chroma != 0 );
+    const uint32_t flags = ( order[c0].cls >> 2 ) & 3u;
+    std::vector<PredUnit>& units = flags ? unitsEx : unitsPlain;
+    TileShape ts = tileShape( f.width, f.height, f.chroma != 0 );
+    if( flags & VVHIP_PRED_EXT_BDOF )
+    {
+      ts.tw = std::min<int>( f.width, 16 ); ts.th = std::min<int>( f.height, 16 );
+      ts.log2SegsRow = ilog2i( ts.tw / 8 ); ts.log2Lanes = ts.log2SegsRow + ilog2i( ts.th );
+    }
     const int subsPerWave = 64 >> ts.log2Lanes, nt = tapsOfKind( ts.kind );
-    ldsPerWave = std::max( ldsPerWave, subsPerWave * subElems( ts.tw, ts.th, nt ) );
+    if( flags ) ldsPerWaveEx = std::max( ldsPerWaveEx, subsPerWave * ( subElems( ts.tw, ts.th, nt ) + ( ( flags & VVHIP_PRED_EXT_BDOF ) ? bdofElems( ts.tw, ts.th ) : 0 ) ) );
+    else ldsPerWave = std::max( ldsPerWave, subsPerWave * subElems( ts.tw, ts.th, nt ) );
     const size_t firstSub = subs.size();
     for( int k = c0; k < c1; k++ )
       for( int y0 = 0; y0 < f.height; y0 += ts.th ) for( int x0 = 0; x0 < f.width; x0 += ts.tw ) subs.push_back( PredSub{ order[k].idx, ( int16_t ) x0, ( int16_t ) y0 } );
@@ -418,7 +643,7 @@ int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_
     {
       const int q = perm[l] * 4 + wv;
       PredUnit u; memset( &u, 0, sizeof( u ) );
-      u.tw = ( int16_t ) ts.tw; u.th = ( int16_t ) ts.th; u.kind = ( uint8_t ) ts.kind; u.log2Lanes = ( uint8_t ) ts.log2Lanes; u.log2SegsRow = ( uint8_t ) ts.log2SegsRow;
+      u.tw = ( int16_t ) ts.tw; u.th = ( int16_t ) ts.th; u.kind = ( uint8_t ) ts.kind; u.log2Lanes = ( uint8_t ) ts.log2Lanes; u.log2SegsRow = ( uint8_t ) ts.log2SegsRow; u.pad[0] = ( uint8_t ) flags;
       if( q < nWaves ) { u.firstSub = ( int32_t ) ( firstSub + ( size_t ) q * subsPerWave ); u.nSub = ( int16_t ) std::min( subsPerWave, nSubs - q * subsPerWave ); }
       units.push_back( u );
     }
@@ -426,6 +651,8 @@ int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_
   }
 
   // ---- device copy of the schedule: grow-only; the host copy stays alive as the source of the asynchronous upload
+  std::vector<PredUnit> units( unitsPlain );      // one table: the plain units, then the units of the extension kernel
+  units.insert( units.end(), unitsEx.begin(), unitsEx.end() );
   const size_t bItems = ( dev.size() * sizeof( PredDev ) + 255 ) & ~( size_t ) 255, bSubs = ( subs.size() * sizeof( PredSub ) + 255 ) & ~( size_t ) 255, bUnits = units.size() * sizeof( PredUnit );
   if( ctx->predEventRecorded ) VVHIP_CHECK_HIP( ctx, hipEventSynchronize( ctx->predEvent ) );      // the last launch that reads the old schedule, whatever stream it went to
   ctx->predKey.clear();
@@ -443,17 +670,14 @@ int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_
   memcpy( ctx->predBlob.data() + bItems + bSubs, units.data(), bUnits );
   VVHIP_CHECK_HIP( ctx, hipMemcpyAsync( ctx->d_predSched, ctx->predBlob.data(), ctx->predBlob.size(), hipMemcpyHostToDevice, ctx->stream ) );
   ctx->predStream = ctx->stream;
-  ctx->predOffSubs = bItems; ctx->predOffUnits = bItems + bSubs; ctx->predUnits = ( int ) units.size(); ctx->predLdsPerWave = ldsPerWave;
+  ctx->predOffSubs = bItems; ctx->predOffUnits = bItems + bSubs; ctx->predUnits = ( int ) unitsPlain.size(); ctx->predLdsPerWave = ldsPerWave;
+  ctx->predUnitsEx = ( int ) unitsEx.size(); ctx->predLdsPerWaveEx = ldsPerWaveEx;
   ctx->predKey.swap( key );
   return VVHIP_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int vvhip_pred_inter_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, int n, int bit_depth,
-                            int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
+int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host, int n, int bit_depth,
+                    int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
 {
   if( !ctx ) return VVHIP_E_ARG;
   if( !planes_host || n_planes < 1 || n_planes > 16 || n < 0 || n > ( 1 << 24 ) || bit_depth < 8 || bit_depth > 12 || pred_stride < 0 || ( n && ( !items_host || !d_pred ) ) || ( d_resi && !d_org ) )
@@ -465,13 +689,16 @@ int vvhip_pred_inter_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, i
   if( n == 0 ) return VVHIP_OK;
 
   // ---- a list that is run again (same items, same plane table) is launched at once: no sort, no upload, no allocation, no wait — such a call can be recorded in a launch graph
-  std::vector<unsigned char> key( sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ) + ( size_t ) n * sizeof( vvhip_pred_item ) );
+  //      (the extensions are part of the list: the same items with other extensions are another schedule)
+  const size_t bKeyItems = sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ) + ( size_t ) n * sizeof( vvhip_pred_item );
+  std::vector<unsigned char> key( bKeyItems + ( ext_host ? ( size_t ) n * sizeof( vvhip_pred_ext ) : 0 ) );
+  if( ext_host ) memcpy( key.data() + bKeyItems, ext_host, ( size_t ) n * sizeof( vvhip_pred_ext ) );
   memcpy( key.data(), &n_planes, sizeof( int ) );
   memcpy( key.data() + sizeof( int ), planes_host, ( size_t ) n_planes * sizeof( vvhip_me_plane ) );
   memcpy( key.data() + sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ), items_host, ( size_t ) n * sizeof( vvhip_pred_item ) );
   if( key != ctx->predKey )
   {
-    const int rc = predBuildSchedule( ctx, planes_host, n_planes, items_host, n, key );
+    const int rc = predBuildSchedule( ctx, planes_host, n_planes, items_host, ext_host, n, key );
     if( rc ) return rc;
   }
   else if( ctx->predStream != ctx->stream )      // same schedule, other stream: order it behind the upload
@@ -486,8 +713,17 @@ int vvhip_pred_inter_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, i
   a.items = reinterpret_cast<const PredDev*>( base ); a.subs = reinterpret_cast<const PredSub*>( base + bItems ); a.units = reinterpret_cast<const PredUnit*>( base + bItems + bSubs );
   a.nUnits = nUnits; a.bitDepth = bit_depth; a.ldsPerWave = ldsPerWave;
   a.pred = d_pred; a.predStride = pred_stride; a.org = d_resi ? d_org : nullptr; a.orgStride = org_stride; a.resi = d_resi;
-  hipLaunchKernelGGL( predListKernel, dim3( ( unsigned ) ( nUnits / 4 ) ), dim3( 256 ), ( size_t ) ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a );
-  VVHIP_LAUNCH_CHECK( ctx );
+  if( nUnits )
+  {
+    hipLaunchKernelGGL( predListKernel, dim3( ( unsigned ) ( nUnits / 4 ) ), dim3( 256 ), ( size_t ) ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a );
+    VVHIP_LAUNCH_CHECK( ctx );
+  }
+  if( ctx->predUnitsEx )
+  {
+    a.units += nUnits; a.nUnits = ctx->predUnitsEx; a.ldsPerWave = ctx->predLdsPerWaveEx;
+    hipLaunchKernelGGL( predListExKernel, dim3( ( unsigned ) ( a.nUnits / 4 ) ), dim3( 256 ), ( size_t ) a.ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a );
+    VVHIP_LAUNCH_CHECK( ctx );
+  }
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if( hipStreamIsCapturing( ctx->stream, &cap ) != hipSuccess ) cap = hipStreamCaptureStatusNone;
   if( cap == hipStreamCaptureStatusNone )      // (a launch recorded into a graph runs later: the graph's owner keeps the list unchanged while the graph is in use)
@@ -497,6 +733,22 @@ int vvhip_pred_inter_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, i
     ctx->predEventRecorded = true;
   }
   return VVHIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int vvhip_pred_inter_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, int n, int bit_depth,
+                            int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
+{
+  return predInterBatch( ctx, planes_host, n_planes, items_host, nullptr, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
+}
+
+int vvhip_pred_inter_batch_ex( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host, int n, int bit_depth,
+                               int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
+{
+  return predInterBatch( ctx, planes_host, n_planes, items_host, ext_host, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
 }
 
 int vvhip_interp_chroma_batch( vvhip_ctx* ctx, const int16_t* d_ref, int ref_stride, const vvhip_subpel_item* d_items, int n,

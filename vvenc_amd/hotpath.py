@@ -25,6 +25,46 @@ DMVR_RESULT_DTYPE = np.dtype([("mvd_x", "<i2"), ("mvd_y", "<i2"), ("pad", "<i4")
 SUBPEL_DTYPE = np.dtype([("org_off", "<i4"), ("ref_off", "<i4"), ("frac_x", "<i2"), ("frac_y", "<i2")])
 PRED_ITEM_DTYPE = np.dtype([("dst_off", "<i4"), ("org_off", "<i4"), ("ref_off", "<i4", (2,)), ("frac", "<i2", (2, 2)), ("width", "<i2"), ("height", "<i2"),
                             ("ref_plane", "i1", (2,)), ("chroma", "u1"), ("alt_hpel", "u1")])      # vvhip_pred_item (32 bytes)
+PRED_EXT_DTYPE = np.dtype([("flags", "u1"), ("pad_dx", "i1", (2,)), ("pad_dy", "i1", (2,)), ("rsv", "u1", (3,))])      # vvhip_pred_ext (8 bytes)
+PRED_EXT_BDOF, PRED_EXT_DMVR_PAD = 1, 2
+
+
+def dmvr_pred_items(results, start_mv, pos, ref_planes, strides, dx, dy, bdof=True, chroma_planes=None, chroma_strides=None):
+    """the final motion compensation of DMVR sub-blocks as a prediction list (DMVR::xFinalPaddedMCForDMVR, CommonLib/InterPrediction.cpp:1189-1225).
+    results = DMVR_RESULT_DTYPE records of vvhip_dmvr_refine_batch; start_mv[i][l] = the (clipped) merge vector (x, y) of list l in 1/16 sample; pos[i] = the sub-block's
+    luma position (x, y) in the picture (plane coordinates, margins included); ref_planes = (plane index of list 0, of list 1), strides their row pitches; dx, dy the
+    sub-block size.  List 0 moves by +mvd, list 1 by -mvd; the integer deltas are ( refined >> shift ) - ( start >> shift ) per component scale; BDOF is the caller's flag
+    AND min_cost >= 2 * dx * dy (:1307, :1384).  With chroma_planes = ((cb0, cb1), (cr0, cr1)) two 4:2:0 chroma items per sub-block follow the luma items.
+    -> (items, ext): PRED_ITEM_DTYPE / PRED_EXT_DTYPE records, dst_off / org_off zero (the caller lays the output out)."""
+    res = np.ascontiguousarray(results).view(DMVR_RESULT_DTYPE).reshape(-1)
+    n = res.size
+    comps = [(0, ref_planes, strides, dx, dy)]
+    for pl in (chroma_planes or ()):
+        comps.append((1, pl, chroma_strides, dx // 2, dy // 2))
+    items, ext = np.zeros(n * len(comps), PRED_ITEM_DTYPE), np.zeros(n * len(comps), PRED_EXT_DTYPE)
+    for c, (chroma, planes, strd, w, h) in enumerate(comps):
+        shift = 4 + chroma
+        for i in range(n):
+            k = c * n + i
+            it, e = items[k], ext[k]
+            it["width"], it["height"], it["chroma"], it["ref_plane"] = w, h, chroma, planes
+            mvd = (int(res[i]["mvd_x"]), int(res[i]["mvd_y"]))
+            moved = False
+            for l in (0, 1):
+                sx, sy = int(start_mv[i][l][0]), int(start_mv[i][l][1])
+                rx, ry = (sx + mvd[0], sy + mvd[1]) if l == 0 else (sx - mvd[0], sy - mvd[1])
+                px, py = int(pos[i][0]) >> chroma, int(pos[i][1]) >> chroma
+                it["ref_off"][l] = (py + (ry >> shift)) * strd[l] + px + (rx >> shift)
+                it["frac"][l] = (rx & ((1 << shift) - 1), ry & ((1 << shift) - 1))
+                e["pad_dx"][l], e["pad_dy"][l] = (rx >> shift) - (sx >> shift), (ry >> shift) - (sy >> shift)
+                moved = moved or e["pad_dx"][l] != 0 or e["pad_dy"][l] != 0
+            fl = PRED_EXT_DMVR_PAD if moved else 0
+            if not moved:
+                e["pad_dx"], e["pad_dy"] = 0, 0
+            if not chroma and bdof and int(res[i]["min_cost"]) >= 2 * dx * dy:
+                fl |= PRED_EXT_BDOF
+            e["flags"] = fl
+    return items, ext
 STATS_DTYPE = np.dtype([("abs_sum", "<i4"), ("last_scan_pos", "<i4"), ("need_rdoq", "<i4"), ("pad", "<i4"), ("sse", "<u8")])
 
 
@@ -523,12 +563,21 @@ class HotPath:
     class _MePlane(C.Structure):          # vvhip_me_plane
         _fields_ = [("d_base", C.c_void_p), ("stride", C.c_int32), ("reserved", C.c_int32)]
 
-    def pred_inter_batch(self, planes, items, pred, pred_stride=0, bit_depth=10, org=None, resi=None):
+    def pred_inter_batch(self, planes, items, pred, pred_stride=0, bit_depth=10, org=None, resi=None, ext=None):
         """inter prediction of a list of prediction units in one launch: planes = the reference Planes the items' ref_plane indexes, items = PRED_ITEM_DTYPE records
         (HOST array: the library sorts it into size classes), pred = int16 tensor (compact blocks at dst_off, or a plane of row pitch pred_stride).
-        org (a Plane) + resi (int16 tensor laid out like pred): also writes org - pred."""
+        org (a Plane) + resi (int16 tensor laid out like pred): also writes org - pred.
+        ext = PRED_EXT_DTYPE records parallel to items (BDOF, DMVR's padded reference): vvhip_pred_inter_batch_ex."""
         it = np.ascontiguousarray(items, PRED_ITEM_DTYPE)
         tab = (self._MePlane * max(1, len(planes)))(*[self._MePlane(p.buf_ptr.value, p.stride, 0) for p in planes])
+        if ext is not None:
+            ex = np.ascontiguousarray(ext, PRED_EXT_DTYPE)
+            if ex.size != it.size:
+                raise ValueError("pred_inter_batch: %d extensions for %d items" % (ex.size, it.size))
+            self._ck(self.L.vvhip_pred_inter_batch_ex(self.ctx, C.cast(tab, C.c_void_p), len(planes), it.ctypes.data_as(C.c_void_p) if it.size else None,
+                                                      ex.ctypes.data_as(C.c_void_p) if ex.size else None, int(it.size), bit_depth, _ptr(pred), pred_stride,
+                                                      org.buf_ptr if org is not None else None, org.stride if org is not None else 0, _ptr(resi)))
+            return pred
         self._ck(self.L.vvhip_pred_inter_batch(self.ctx, C.cast(tab, C.c_void_p), len(planes), it.ctypes.data_as(C.c_void_p) if it.size else None, int(it.size), bit_depth,
                                                _ptr(pred), pred_stride, org.buf_ptr if org is not None else None, org.stride if org is not None else 0, _ptr(resi)))
         return pred
