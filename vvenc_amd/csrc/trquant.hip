@@ -1097,6 +1097,25 @@ tuMxBody( int16_t* __restrict__ stage, int32_t* __restrict__ sInit, v4i* __restr
       aLo[g] = ( int ) ( __builtin_amdgcn_perm( xr[2 * g + 1], xr[2 * g], 0x06040200u ) ^ 0x80808080u );
       aHi[g] = ( int ) __builtin_amdgcn_perm( xr[2 * g + 1], xr[2 * g], 0x07050301u );
     }
+    // the residual's energy per TU slot of the lane and its +-4095 test, taken where the first read's registers die: an all-zero tile's SSE is that energy (see below).
+    // Run c of the lane belongs to slot ( PS * c ) / N, as in TUMX_TAIL; lanes beyond the list hold zeros.  16 squares of up to 2^24 fit 32 bits.
+    int eng[R];
+    bool smallResi = false;
+    if( N >= TUMX_ZERO_MIN_N )
+    {
+      typedef unsigned short u16x2e __attribute__( ( ext_vector_type( 2 ) ) );
+      uint32_t magn = 0;
+#pragma unroll
+      for( int r = 0; r < R; r++ ) eng[r] = 0;
+#pragma unroll
+      for( int k = 0; k < 8; k++ )
+      {
+        const int slot = ( PS * ( k / ( PS / 2 ) ) ) / N < R ? ( PS * ( k / ( PS / 2 ) ) ) / N : 0;
+        eng[slot] = dot2( xr[k], xr[k], eng[slot] );
+        magn |= __builtin_bit_cast( uint32_t, __builtin_bit_cast( u16x2e, xr[k] ) + __builtin_bit_cast( u16x2e, 0x10001000u ) ) & 0xe000e000u;
+      }
+      smallResi = __builtin_amdgcn_ballot_w64( magn != 0 ) == 0ull;      // (wave-uniform: an SGPR pair, not a register, through the forward passes)
+    }
     vvhip_tu_qp qqs[R];                                               // QPs of the lane's TUs on the coefficient side: column block blkL, row blocks blk0 + r
 #pragma unroll
     for( int r = 0; r < R; r++ ) { const int tu = tile * TPT + ( blk0 + r ) * TPS + blkL; qqs[r] = tu < A.n ? A.qps[tu] : vvhip_tu_qp{ 32, 0 }; }
@@ -1257,15 +1276,6 @@ _Pragma( "unroll" ) \
       } }
     if( allZero )
     {
-      // (keeping the first read's registers alive instead — -DTUMX_ZERO_KEEP_RESI=1 — makes all-zero 32-point lists 12 % faster on their own, 17.9 -> 15.7 us for 8 192 tiles,
-      //  and the five-stream step of the recorded lists 5 % SLOWER, 66.2 -> 70.8 us: measured twice each in one call, profiles/r05_tu_zero_shortcut.log; not the default)
-#if TUMX_ZERO_KEEP_RESI
-#pragma unroll
-      for( int k = 0; k < 8; k++ ) xr2[k] = xr[k];
-#else
-      TUMX_REREAD()
-#endif
-      //                                               // (requested first: the zero stores below pass under its latency)
 #pragma unroll
       for( int r = 0; r < R; r++ )
       {
@@ -1293,6 +1303,20 @@ _Pragma( "unroll" ) \
           else          { if( A.level ) *reinterpret_cast<u32x2*>( A.level + at ) = u32x2{ 0, 0 }; if( A.rec ) *reinterpret_cast<u32x2*>( A.rec + at ) = u32x2{ 0, 0 }; }
         }
       }
+      if( smallResi )
+      {
+        // no second read: the group sums of the energies taken at the first one (64-bit sums of 32-bit lane values, as TUMX_TAIL: 1 024 squares of up to 2^24 do not fit 32 bits)
+#pragma unroll
+        for( int r = 0; r < R; r++ )
+        {
+          const unsigned long long t = vvhipGroupSum64( ( unsigned long long ) ( uint32_t ) eng[r], G, lane );
+          const int tu = tile * TPT + blkL * TPS + blk0 + r;
+          if( A.stats && ( N < 32 || h == 0 ) && inL == r && tu < A.n ) A.stats[tu].sse = t;
+        }
+        continue;
+      }
+      // any sample of the wave outside +-4095 (no residual of <= 12-bit video; arbitrary int16 input): a second read and the exact 64-bit squares of TUMX_TAIL
+      TUMX_REREAD()
 #pragma unroll
       for( int v = 0; v < 16; v++ ) d[v] = 0;
       TUMX_TAIL( false )
@@ -1458,6 +1482,11 @@ tuMx64Body( int16_t* __restrict__ stage, int32_t* __restrict__ sInit /* [96] */,
     const vvhip_tu_qp qq = A.qps[tu];
     int d[16];
     v4i bLo[2], bHi[2];
+    // the residual's energy and its +-4095 test are taken HERE, from the registers of the first (only) read of the four chunks: an all-zero TU's SSE is that energy (see
+    // below).  -4096 <= x <= 4095 on all 64 samples of a lane -> the lane's sum of squares is <= 64 * 2^24 = 2^30: one 32-bit accumulator (v_dot2_i32_i16) and one mask
+    typedef unsigned short u16x2z __attribute__( ( ext_vector_type( 2 ) ) );
+    int eng = 0;
+    uint32_t magn = 0;
     // ---- forward rows, two row tiles: tmp[y][k] = sat16( ( sum_{x<64} blk[y][x] * T[k][x] + rnd ) >> shift1 ), k < 32            (TrQuant.cpp:548)
 #pragma unroll
     for( int t = 0; t < 2; t++ )
@@ -1477,6 +1506,12 @@ tuMx64Body( int16_t* __restrict__ stage, int32_t* __restrict__ sInit /* [96] */,
         {
           aLo[c][g] = ( int ) ( __builtin_amdgcn_perm( xr[2 * g + 1], xr[2 * g], 0x06040200u ) ^ 0x80808080u );
           aHi[g] = ( int ) __builtin_amdgcn_perm( xr[2 * g + 1], xr[2 * g], 0x07050301u );
+        }
+#pragma unroll
+        for( int k = 0; k < 8; k++ )
+        {
+          eng = dot2( xr[k], xr[k], eng );
+          magn |= __builtin_bit_cast( uint32_t, __builtin_bit_cast( u16x2z, xr[k] ) + __builtin_bit_cast( u16x2z, 0x10001000u ) ) & 0xe000e000u;
         }
         acc = __builtin_amdgcn_mfma_i32_32x32x32_i8( aHi, sOps[c * 64 + lane], acc, 0, 0, 0 );
       }
@@ -1541,47 +1576,44 @@ tuMx64Body( int16_t* __restrict__ stage, int32_t* __restrict__ sInit /* [96] */,
         int32_t* st = reinterpret_cast<int32_t*>( A.stats + tu );
         st[0] = 0; st[1] = ( int32_t ) last; st[2] = ( int32_t ) need; st[3] = 0;
       }
-      unsigned long long sse0 = 0;
-      typedef unsigned short u16x2z __attribute__( ( ext_vector_type( 2 ) ) );
+      // (levels and reconstruction zeros in raster runs: whole 64-byte requests; 512 runs of 8 samples per array, 8 per lane)
+      // (sparse outputs: nothing but the statistics for a TU whose levels are all zero, see tuMxBody)
+      if( !( A.phaseLimit & 0x100 ) )
+      {
+        // (a wave-uniform base per TU and array + one 32-bit lane offset)
+        char* zr = reinterpret_cast<char*>( A.rec + ( size_t ) tu * 4096 );
+        char* zl = reinterpret_cast<char*>( A.level + ( size_t ) tu * 4096 );
+        uint32_t zo = ( uint32_t ) lane * 16u;
+        asm volatile( "" : "+v"( zo ) );      // (opaque: made here, not carried through the loop)
+        const u32x4 z4 = { 0, 0, 0, 0 };
+#pragma unroll
+        for( int u = 0; u < 8; u++ )
+        {
+          if( A.rec ) *reinterpret_cast<u32x4*>( zr + ( zo + 1024u * u ) ) = z4;
+          if( A.level ) *reinterpret_cast<u32x4*>( zl + ( zo + 1024u * u ) ) = z4;
+        }
+      }
+      unsigned long long sse0 = ( unsigned long long ) ( uint32_t ) eng;
+      // any sample of the wave outside +-4095 (no residual of <= 12-bit video; arbitrary int16 input): the exact 64-bit squares of a second read, chunk by chunk
+      if( __builtin_amdgcn_ballot_w64( magn != 0 ) != 0ull )
+      {
+        sse0 = 0;
 #pragma nounroll
-      for( int tc = 0; tc < 4; tc++ )                                  // (not unrolled: four chunks' requests at once would cost the long way's registers)
+        for( int tc = 0; tc < 4; tc++ )
         {
           const int t = tc >> 1, c = tc & 1;
           const int16_t* p = src + ( ptrdiff_t ) ( 32 * t + c32 ) * resiStride + 32 * c + 16 * h;
           const u32x4 x0 = reinterpret_cast<const U16*>( p )->v, x1 = reinterpret_cast<const U16*>( p + 8 )->v;
           const uint32_t xr[8] = { x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w };
-          const u32x4 z4 = { 0, 0, 0, 0 };
-          // (levels and reconstruction zeros in the same raster runs: whole 64-byte requests; 512 runs of 8 samples per array, 2 per lane and chunk)
-          const int q0 = lane + 64 * ( 4 * t + 2 * c );
-          const bool dense = !( A.phaseLimit & 0x100 );      // (sparse outputs: nothing but the statistics for a TU whose levels are all zero, see tuMxBody)
-          if( A.rec && dense )
-          {
-            *reinterpret_cast<u32x4*>( A.rec + ( size_t ) tu * 4096 + ( size_t ) q0 * 8 ) = z4;
-            *reinterpret_cast<u32x4*>( A.rec + ( size_t ) tu * 4096 + ( size_t ) ( q0 + 64 ) * 8 ) = z4;
-          }
-          if( A.level && dense )
-          {
-            *reinterpret_cast<u32x4*>( A.level + ( size_t ) tu * 4096 + ( size_t ) q0 * 8 ) = z4;
-            *reinterpret_cast<u32x4*>( A.level + ( size_t ) tu * 4096 + ( size_t ) ( q0 + 64 ) * 8 ) = z4;
-          }
-          uint32_t magn = 0;
 #pragma unroll
-          for( int k = 0; k < 8; k++ ) magn |= __builtin_bit_cast( uint32_t, __builtin_bit_cast( u16x2z, xr[k] ) + __builtin_bit_cast( u16x2z, 0x10001000u ) ) & 0xe000e000u;
-          if( __builtin_amdgcn_ballot_w64( magn != 0 ) == 0ull )
+          for( int k = 0; k < 8; k++ )
           {
-            uint32_t s32 = 0;
-#pragma unroll
-            for( int k = 0; k < 8; k++ ) s32 = ( uint32_t ) dot2( xr[k], xr[k], ( int ) s32 );
-            sse0 += s32;
+            const int e0 = ( int ) ( int16_t ) ( xr[k] & 0xffff ), e1 = ( int ) xr[k] >> 16;
+            sse0 += ( unsigned long long ) ( ( long long ) e0 * e0 ) + ( unsigned long long ) ( ( long long ) e1 * e1 );
           }
-          else
-#pragma unroll
-            for( int k = 0; k < 8; k++ )
-            {
-              const int e0 = ( int ) ( int16_t ) ( xr[k] & 0xffff ), e1 = ( int ) xr[k] >> 16;
-              sse0 += ( unsigned long long ) ( ( long long ) e0 * e0 ) + ( unsigned long long ) ( ( long long ) e1 * e1 );
-            }
         }
+      }
+      // (a 64-bit group sum in both cases: 4 096 squares of up to 2^24 do not fit 32 bits — the dropped high frequencies can carry any energy past an all-zero quantiser)
       sse0 = vvhipGroupSum64( sse0, 64, lane );
       if( A.stats && lane == 0 ) A.stats[tu].sse = sse0;
       continue;
@@ -1615,12 +1647,17 @@ tuMx64Body( int16_t* __restrict__ stage, int32_t* __restrict__ sInit /* [96] */,
       st[0] = ( int32_t ) sum; st[1] = ( int32_t ) last; st[2] = ( int32_t ) need; st[3] = 0;
     }
     WAVE_SYNC();
+    // (the lane index behind an opaque copy from here on: the addresses of the long way — raster runs, operand records, reconstruction rows — are then recomputed per TU
+    //  that gets this far instead of sitting in ~25 registers through the forward passes of EVERY TU as loop invariants)
+    int laneL = lane;
+    asm volatile( "" : "+v"( laneL ) );
+    const int hL = laneL >> 5, c32L = laneL & 31;
     // ---- levels: 64x64 raster, the 32x32 region from the staging tile, zeros elsewhere (512 runs of 8 samples, 8 per lane)
     if( A.level )
 #pragma unroll
       for( int u = 0; u < 8; u++ )
       {
-        const int q = lane + 64 * u, Y = q >> 3, X = 8 * ( q & 7 );
+        const int q = laneL + 64 * u, Y = q >> 3, X = 8 * ( q & 7 );
         u32x4 v = { 0, 0, 0, 0 };
         if( Y < 32 && X < 32 ) v = *reinterpret_cast<const u32x4*>( &stage[Y * LP + X] );
         *reinterpret_cast<u32x4*>( A.level + ( size_t ) tu * 4096 + Y * 64 + X ) = v;
@@ -1635,7 +1672,7 @@ tuMx64Body( int16_t* __restrict__ stage, int32_t* __restrict__ sInit /* [96] */,
       v16i c;
 #pragma unroll
       for( int v = 0; v < 16; v++ ) c[v] = cI1[t];
-      const v4i op = *reinterpret_cast<const v4i*>( O->natTY[t][lane] );
+      const v4i op = *reinterpret_cast<const v4i*>( O->natTY[t][laneL] );
       v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8( aHi, op, zero16, 0, 0, 0 );
 #pragma unroll
       for( int v = 0; v < 16; v++ ) acc[v] = ( acc[v] << 8 ) + c[v];
@@ -1645,19 +1682,20 @@ tuMx64Body( int16_t* __restrict__ stage, int32_t* __restrict__ sInit /* [96] */,
       mxSplitSat( d, bLo[t], bHi[t] );
     }
     // ---- inverse rows: rec[y][x] = clip( ( sum_{k<32} t1[y][k] * T[k][x] + rnd ) >> shift2 ), row tile t x column chunk c; SSE vs the residual (:613)
+    // (column chunk outside, row tile inside: the chunk's preload and operand record are fetched once and die with the chunk)
     unsigned long long sse = 0;
 #pragma unroll
-    for( int t = 0; t < 2; t++ )
+    for( int c = 0; c < 2; c++ )
 #pragma unroll
-      for( int c = 0; c < 2; c++ )
+      for( int t = 0; t < 2; t++ )
       {
         const int16_t* p = src + ( ptrdiff_t ) ( 32 * t + c32 ) * resiStride + 32 * c + 16 * h;
         const u32x4 x0 = reinterpret_cast<const U16*>( p )->v, x1 = reinterpret_cast<const U16*>( p + 8 )->v;
         const uint32_t xr[8] = { x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w };
         v16i ci;
 #pragma unroll
-        for( int g = 0; g < 4; g++ ) { const v4i t4 = *reinterpret_cast<const v4i*>( &sInit[32 + 32 * c + h * 16 + 4 * g] ); ci[4 * g] = t4.x; ci[4 * g + 1] = t4.y; ci[4 * g + 2] = t4.z; ci[4 * g + 3] = t4.w; }
-        const v4i op = *reinterpret_cast<const v4i*>( O->colPX[c][lane] );
+        for( int g = 0; g < 4; g++ ) { const v4i t4 = *reinterpret_cast<const v4i*>( &sInit[32 + 32 * c + hL * 16 + 4 * g] ); ci[4 * g] = t4.x; ci[4 * g + 1] = t4.y; ci[4 * g + 2] = t4.z; ci[4 * g + 3] = t4.w; }
+        const v4i op = *reinterpret_cast<const v4i*>( O->colPX[c][laneL] );
         v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8( op, bHi[t], zero16, 0, 0, 0 );
 #pragma unroll
         for( int v = 0; v < 16; v++ ) acc[v] = ( acc[v] << 8 ) + ci[v];
@@ -1693,7 +1731,7 @@ tuMx64Body( int16_t* __restrict__ stage, int32_t* __restrict__ sInit /* [96] */,
           }
         if( A.rec )
         {
-          int16_t* dst = A.rec + ( size_t ) tu * 4096 + ( 32 * t + c32 ) * 64 + 32 * c + 16 * h;
+          int16_t* dst = A.rec + ( size_t ) tu * 4096 + ( 32 * t + c32L ) * 64 + 32 * c + 16 * hL;
           u32x4 a, b; a.x = rp[0]; a.y = rp[1]; a.z = rp[2]; a.w = rp[3]; b.x = rp[4]; b.y = rp[5]; b.z = rp[6]; b.w = rp[7];
           *reinterpret_cast<u32x4*>( dst ) = a; *reinterpret_cast<u32x4*>( dst + 8 ) = b;
         }
@@ -1931,26 +1969,29 @@ tuMx64PairBody( int16_t* __restrict__ stage, int32_t* __restrict__ sInit /* [96]
 struct TuMxJobs { int nJobs; int pair64; int waveStart[8]; int size[8]; TuMxArgs j[8]; };
 
 // Three instances, by what the launch's lists need: KIND 0 the 8/16/32-point bodies, KIND 1 also the 4-point body (four TUs per lane), KIND 2 also the 64-point body.
-// Registers (round 5, tools/kernel_regs.py): 148 / 164 / 166, no scratch — every instance runs three waves per SIMD.  Round 4 held 168 (1 spill) / 168 (33 spills) / 232 (two waves
+// Registers (tools/kernel_regs.py; profiles/tu_zero_path.md): 164 / 166 / 168 with the residual energy taken at the first read (round 5: 148 / 164 / 166), no scratch — every instance runs three waves per SIMD.  Round 4 held 168 (1 spill) / 168 (33 spills) / 232 (two waves
 // per SIMD for EVERY size of a launch with 64x64 TUs): each 1-D pass kept the high-byte and the low-byte product in two 16-register accumulators side by side; the passes now run the
 // high-byte product first and the low-byte product on top of it (MX_PASS), and the 64-point body takes its SSE through the packed 32-bit form like the others.
 // Measured (recorded 1080p mix, same box): the TU launch alone 17.75 -> 16.9 us, the five-stream step 73.0 -> 69.1 us (the freed registers let the other streams' waves share the SIMDs).
 // Throughput of the 32-point lists is 467 tiles/us = 80 % of the VALU issue bound (1 059 wave instructions per tile): the instruction count, not occupancy, is what is left.
 // KIND 3 = KIND 2 with a 64x64 TU over a wave pair (tuMx64PairBody, $VVHIP_TU_PAIR64=1: measured slower, not the default) — its own instance because the pair's exchange area
 // is 17 KB of LDS per workgroup that the default launch must not reserve (the TU workgroups share their CUs with the motion-search kernels of the other streams).
-template<int KIND>
-__global__ void __launch_bounds__( 256, KIND == 3 ? 2 : 3 )
+// WPB = waves per workgroup: 1 (the default) or 4 ($VVHIP_TU_WG1=0, see tuRdoMulti) — the waves of a workgroup share nothing (their LDS is per wave, there is no barrier outside
+// the pair form), so a one-wave workgroup is the same work placed wave by wave instead of four SIMDs of one CU at a time.
+template<int KIND, int WPB>
+__global__ void __launch_bounds__( 64 * WPB, KIND == 3 ? 2 : 3 )
 tuMxMultiKernel( const int16_t* __restrict__ resi, int resiStride, TuMxJobs jobs )
 {
   constexpr bool WITH4 = KIND >= 1, WITH64 = KIND >= 2, PAIR64 = KIND == 3;
-  __shared__ __attribute__( ( aligned( 16 ) ) ) int16_t stage[4][32 * 40];
-  __shared__ __attribute__( ( aligned( 16 ) ) ) int32_t sInit[4][WITH64 ? 96 : 64];
-  __shared__ v4i sOps[4][PAIR64 ? 512 : ( WITH64 ? 256 : 128 )];      // forward-pass operands per wave (8/16/32-point: 2 slots, 64-point: 4; the pair form keeps all 8)
+  static_assert( WPB == 4 || ( WPB == 1 && !PAIR64 ), "the pair form needs both waves of a pair in one workgroup" );
+  __shared__ __attribute__( ( aligned( 16 ) ) ) int16_t stage[WPB][32 * 40];
+  __shared__ __attribute__( ( aligned( 16 ) ) ) int32_t sInit[WPB][WITH64 ? 96 : 64];
+  __shared__ v4i sOps[WPB][PAIR64 ? 512 : ( WITH64 ? 256 : 128 )];      // forward-pass operands per wave (8/16/32-point: 2 slots, 64-point: 4; the pair form keeps all 8)
   __shared__ int32_t xch[PAIR64 ? 2 : 1][PAIR64 ? 2 * 64 * 17 : 1];      // 64x64 TUs over a wave pair: the pair's exchange area
   __shared__ uint32_t pairCtr[2];
   if( PAIR64 ) { if( threadIdx.x < 2 ) pairCtr[threadIdx.x] = 0; __syncthreads(); }      // (before any wave leaves)
-  const int wv = __builtin_amdgcn_readfirstlane( ( int ) ( threadIdx.x >> 6 ) );
-  const int wave = blockIdx.x * 4 + wv;
+  const int wv = WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane( ( int ) ( threadIdx.x >> 6 ) );
+  const int wave = blockIdx.x * WPB + wv;
   int k = 0;
 #pragma unroll
   for( int i = 1; i < 8; i++ ) if( i < jobs.nJobs && wave >= jobs.waveStart[i] ) k = i;
@@ -2441,7 +2482,14 @@ static int tuRdoMulti( vvhip_ctx* ctx, const int16_t* d_resi, int resi_stride, c
       for( int i = 0; i < xj.nJobs; i++ ) any4 |= xj.size[i] == 4 || xj.size[i] == 64;
       bool any64 = false;
       for( int i = 0; i < xj.nJobs; i++ ) any64 |= xj.size[i] == 64;
-      const dim3 grid( ( unsigned ) ( ( waves + 3 ) / 4 ) );
+      // One wave per workgroup (the default; $VVHIP_TU_WG1=0: four, the form up to round 6; the pair form keeps four).  A 256-thread workgroup needs ~168 free registers on all four
+      // SIMDs of ONE CU at the same moment while the other streams' 55-64-register waves refill every slot that frees up; a one-wave workgroup goes wherever one SIMD has room.
+      // Measured in alternating runs on one GPU (profiles/tu_zero_path.md): the launch on its own gets SLOWER, 15.27 -> 15.67 us in the serialized trace and 11.9 -> 12.9 us for the
+      // all-zero five-size mix, and the five-stream step FASTER: `value` 15.8 -> 16.2 k pictures/s in six of six pairs, 4K GOP-weighted 4.90 -> 5.04 k in three of three.
+      // Read per call, as $VVHIP_TU_KERNEL: tests switch it.
+      const char* wg1Env = getenv( "VVHIP_TU_WG1" );
+      const int wpb = ( ( !wg1Env || atoi( wg1Env ) != 0 ) && !( any64 && pair64 ) ) ? 1 : 4;
+      const dim3 grid( ( unsigned ) ( ( waves + wpb - 1 ) / wpb ) );
       // $VVHIP_TU_LDS_PAD: extra LDS bytes reserved per workgroup (unused) = fewer TU workgroups per CU.  A TU wave holds 168 / 232 registers: three / two of them fill a SIMD's
       // register file and nothing of the other streams' kernels can share that SIMD while they wait for memory (measurements of the five-stream step: DESIGN 6)
       static const int ldsPad = getenv( "VVHIP_TU_LDS_PAD" ) ? atoi( getenv( "VVHIP_TU_LDS_PAD" ) ) : 0;
@@ -2449,15 +2497,24 @@ static int tuRdoMulti( vvhip_ctx* ctx, const int16_t* d_resi, int resi_stride, c
       if( ldsPad > 0 && !padSet )
       {
         padSet = true;
-        ( void ) hipFuncSetAttribute( ( const void* ) tuMxMultiKernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsPad );
-        ( void ) hipFuncSetAttribute( ( const void* ) tuMxMultiKernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsPad );
-        ( void ) hipFuncSetAttribute( ( const void* ) tuMxMultiKernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsPad );
-        ( void ) hipFuncSetAttribute( ( const void* ) tuMxMultiKernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsPad );
+        ( void ) hipFuncSetAttribute( ( const void* ) tuMxMultiKernel<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsPad );
+        ( void ) hipFuncSetAttribute( ( const void* ) tuMxMultiKernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsPad );
+        ( void ) hipFuncSetAttribute( ( const void* ) tuMxMultiKernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsPad );
+        ( void ) hipFuncSetAttribute( ( const void* ) tuMxMultiKernel<3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsPad );
+        ( void ) hipFuncSetAttribute( ( const void* ) tuMxMultiKernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsPad );
+        ( void ) hipFuncSetAttribute( ( const void* ) tuMxMultiKernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsPad );
+        ( void ) hipFuncSetAttribute( ( const void* ) tuMxMultiKernel<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsPad );
       }
-      if( any64 && pair64 ) hipLaunchKernelGGL( tuMxMultiKernel<3>, grid, dim3( 256 ), ldsPad, ctx->stream, d_resi, resi_stride, xj );
-      else if( any64 ) hipLaunchKernelGGL( tuMxMultiKernel<2>, grid, dim3( 256 ), ldsPad, ctx->stream, d_resi, resi_stride, xj );
-      else if( any4 ) hipLaunchKernelGGL( tuMxMultiKernel<1>, grid, dim3( 256 ), ldsPad, ctx->stream, d_resi, resi_stride, xj );
-      else            hipLaunchKernelGGL( tuMxMultiKernel<0>, grid, dim3( 256 ), ldsPad, ctx->stream, d_resi, resi_stride, xj );
+      if( any64 && pair64 ) hipLaunchKernelGGL( ( tuMxMultiKernel<3, 4> ), grid, dim3( 256 ), ldsPad, ctx->stream, d_resi, resi_stride, xj );
+      else if( wpb == 1 )
+      {
+        if( any64 )     hipLaunchKernelGGL( ( tuMxMultiKernel<2, 1> ), grid, dim3( 64 ), ldsPad, ctx->stream, d_resi, resi_stride, xj );
+        else if( any4 ) hipLaunchKernelGGL( ( tuMxMultiKernel<1, 1> ), grid, dim3( 64 ), ldsPad, ctx->stream, d_resi, resi_stride, xj );
+        else            hipLaunchKernelGGL( ( tuMxMultiKernel<0, 1> ), grid, dim3( 64 ), ldsPad, ctx->stream, d_resi, resi_stride, xj );
+      }
+      else if( any64 ) hipLaunchKernelGGL( ( tuMxMultiKernel<2, 4> ), grid, dim3( 256 ), ldsPad, ctx->stream, d_resi, resi_stride, xj );
+      else if( any4 ) hipLaunchKernelGGL( ( tuMxMultiKernel<1, 4> ), grid, dim3( 256 ), ldsPad, ctx->stream, d_resi, resi_stride, xj );
+      else            hipLaunchKernelGGL( ( tuMxMultiKernel<0, 4> ), grid, dim3( 256 ), ldsPad, ctx->stream, d_resi, resi_stride, xj );
     }
     else
     {
