@@ -442,7 +442,8 @@ VVHIP_API int  vvhip_me_plan_info( const vvhip_me_plan* plan, int* waves_int, in
  * BDOF and the padded-reference rule of DMVR (DMVR::xFinalPaddedMCForDMVR, CommonLib/InterPrediction.cpp:1189-1225: a refined sub-block's final prediction reads a padded
  * copy of its PREFETCHED window, not the true plane) are per-item extensions: vvhip_pred_inter_batch_ex below.  Without them this entry is exact for DMVR sub-blocks whose
  * refinement is zero and for every PU BDOF does not apply to.
- * NOT done here (the caller's job, as before): BCW and explicit weighted prediction; GEO blending; affine / PROF; IBC; reference picture resampling; the chroma phases of 4:2:2 and 4:4:4.
+ * Affine CUs with PROF have an entry of their own that takes the control-point vectors: vvhip_pred_affine_batch below.
+ * NOT done here (the caller's job, as before): BCW and explicit weighted prediction; GEO blending; IBC; reference picture resampling; the chroma phases of 4:2:2 and 4:4:4.
  * ====================================================================================================================== */
 typedef struct
 {
@@ -488,6 +489,49 @@ VVHIP_API int vvhip_pred_inter_batch_ex( vvhip_ctx* ctx, const vvhip_me_plane* p
                                          const vvhip_pred_ext* ext_host /* may be NULL */, int n, int bit_depth,
                                          int16_t* d_pred, int pred_stride,
                                          const int16_t* d_org /* may be NULL */, int org_stride, int16_t* d_resi /* may be NULL */ );
+/* Inter prediction of a LIST of AFFINE CUs from their control-point vectors: what InterPredInterpolation::xPredAffineBlk (CommonLib/InterPrediction.cpp:1497-1839) + the
+ * default weighted average produce for one component block of one affine CU, PROF included, bit-exact.  One item is one component block; the CU record is all that
+ * crosses to the device — the sub-block vectors, fractions and PROF's dMv table are derived in the kernel.
+ *   model     : iDMvHor = ( RT - LT ) << ( 7 - log2 cu_w ); iDMvVer from LB (six_param) or ( -iDMvHorY, iDMvHorX ); base LT << 7 (:1528-1542).  Chroma uses the luma quantities.
+ *   luma 4x4  : the value at the sub-block's centre ( 2 + w, 2 + h ), or at the CU's centre for every sub-block when isSubblockVectorSpreadOverLimit (:1457-1495) holds —
+ *               its predType is 3 when both lists are used, else the one list's interDir; the rule branches on 3 only —, roundAffineMv( ., 7 ) (Mv.cpp:61-66), the 18-bit
+ *               storage clip: the stored vector.  Then the picture clip [ ( -ctu_size - 8 - cu_x + 1 ) << 4, ( pic_width + 8 - cu_x - 1 ) << 4 ], likewise vertically
+ *               (:1545-1550, :1725-1726); position >> 4, fraction & 15.
+ *   chroma 4x4: the stored vectors of its top-left and bottom-right luma sub-blocks summed, roundAffineMv( ., 1 ), the same clip in luma units, >> 5 / & 31 (:1729-1765).
+ *   taps      : as a 4x4 luma / 4x4 chroma item of vvhip_pred_inter_batch (m_lumaFilter4x4, m_chromaFilter): filter4x4 / filterHor / filterVer; isLast = !bi && !PROF.
+ *   prof      : luma only, decided per list.  0: off.  1: on unless the list's control points are all equal (:1557) or the spread is over the limit (:1558) — the conditions
+ *               the library evaluates itself.  2 / 3: additionally the search-time rule of :1559-1560 (m_encOnly && !checkLDC) with threshold 1 << 7 / 1 << 8: on only when a
+ *               model delta exceeds it.  The other conditions (SPS / picture-header flags, m_skipPROF, equal picture sizes) are the caller's.  When on, per sub-block: the dMv
+ *               table (:1583-1630: roundAffineMv( ., 8 ), clip to +-31), the 14-bit block inside a one-sample ring ( ref << shift ) - 8192 at the position rounded by
+ *               frac >> 3 (:1797-1820), gradFilterCore<false> (:113-131), applyPROFCore (:88-111: dI clipped to 1 << max( bit_depth + 1, 13 ), stored as a sample before the
+ *               rounding, no rounding when bi).
+ *   two lists : each to the 14-bit block (with its own PROF decision), then the default average of vvhip_pred_inter_batch.  BDOF never applies to affine CUs; BCW is the caller's.
+ *   output, residual, plane table: as vvhip_pred_inter_batch; a compact block's row pitch is the component block's width ( cu_w >> chroma ).
+ * items_host is a HOST array.  The library keeps a device schedule of its own for this entry (CU records + one 8-byte record per tile of sixteen sub-blocks; own key, buffer and
+ * event): the same list again uploads nothing, and alternating with vvhip_pred_inter_batch on one context evicts neither schedule.  Results do not depend on the list's order.
+ * Read bound: after the picture clip a sub-block reads at most ctu_size + 8 + 3 samples left of / above the picture and at most 8 + cu_w + 3 + 1 ( 8 + cu_h + 3 + 1 ) samples
+ * right of / below it (the + 1: PROF's ring) — with CUs no larger than the CTU inside the reference encoder's own picture margin of ctu_size + 16 —, plus the 16 bytes of the
+ * aligned-dword rule; planes need an even row pitch.
+ * Argument errors (VVHIP_E_ARG with a message naming the entry, nothing launched): a CU size that is not a power of two in 8..128; neither list used; a plane index outside the
+ * table; chroma > 1; six_param > 1; prof > 3; non-zero reserved bytes; a control point outside the 18-bit vector range; ctu_size not 32 / 64 / 128; a CU outside the picture.  */
+typedef struct
+{
+  int32_t dst_off;            /* sample offset of the block in d_pred (and in d_resi)                                  */
+  int32_t org_off;            /* the block in the original plane (residual only)                                       */
+  int32_t ref_off[2];         /* per list: the block's own (collocated, zero-vector) position in plane ref_plane[l]    */
+  int32_t cpmv[2][3][2];      /* per list LT, RT, LB as ( hor, ver ) in 1/16 luma sample; LB ignored unless six_param  */
+  int16_t cu_x, cu_y;         /* the CU in luma samples                                                                */
+  int16_t cu_w, cu_h;         /* independent powers of two, 8..128                                                     */
+  int8_t  ref_plane[2];       /* index into the plane table, -1 = list not used                                        */
+  uint8_t chroma;             /* 0: the cu_w x cu_h luma block, 1: a 4:2:0 chroma block cu_w / 2 x cu_h / 2            */
+  uint8_t six_param;          /* 1: the 6-parameter model                                                              */
+  uint8_t prof;               /* 0..3, see above (luma only)                                                           */
+  uint8_t rsv[3];             /* zero                                                                                  */
+} vvhip_pred_affine_item;     /* 80 bytes */
+VVHIP_API int vvhip_pred_affine_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_affine_item* items_host, int n,
+                                       int pic_width, int pic_height, int ctu_size /* luma: 32, 64, 128 */, int bit_depth,
+                                       int16_t* d_pred, int pred_stride,
+                                       const int16_t* d_org /* may be NULL */, int org_stride, int16_t* d_resi /* may be NULL */ );
 /* The chroma twin of vvhip_interp_luma_batch: n blocks of ONE size (powers of two, 2..64) from one plane, items on the device (frac_x / frac_y in 1/32 sample, org_off unused),
  * compact output d_out[i*w*h + y*w + x]; rnd_res 1 = final samples, 0 = the 14-bit intermediate a bi-prediction average consumes.  Margins as above.                            */
 VVHIP_API int vvhip_interp_chroma_batch( vvhip_ctx* ctx, const int16_t* d_ref, int ref_stride, const vvhip_subpel_item* d_items, int n,

@@ -11,6 +11,10 @@ B. the realistic list: a B picture's mix of prediction units — the fixed histo
    output on.  Reported: time per picture, the bytes the algorithm reads and writes (per list the window (w + taps - 1) x (h + taps - 1), the original block, prediction and
    residual blocks; 2 bytes per sample) and their fraction of the HBM peak, the host time of a first call (sort + schedule + upload) and of a repeated call (the list is
    recognised).  The same list again with BDOF set on its true bi-predicted luma items that pass BDOF's size rule (vvhip_pred_inter_batch_ex), in the same rounds.
+C. the affine mix: seeded affine CUs AFFINE_HIST (sizes 16..64, half bi-predicted, both models, control-point spread D = 32, luma + Cb + Cr, prof = 0) through
+   vvhip_pred_affine_batch, and the same CUs expanded by the host into 4x4 items (tests/affine_ref.expand_items: what a caller had to do before) through
+   vvhip_pred_inter_batch of the same build, in the same rounds; the outputs are compared first.  Then the same mix with prof = 1.  Reported besides the times: the host
+   time of each first call and the bytes of list records and of device schedule each path uploads (from the record sizes of pred.hip / predaffine.hip).
 Every variant is recorded into a launch graph once and timed as `reps` graph launches between two host clock readings that end in a device synchronise, `rounds` times, the
 variants alternating inside a round; medians, minima and the spread ( max - min ) / median are printed.  --quick: one round of few launches (for a profiler run)."""
 import argparse
@@ -30,6 +34,9 @@ HBM_PEAK = 8.0e12          # bytes / s (the figure bench.py's roofline uses)
 # luma prediction units of one B picture: (width, height) -> count.  1.80 of the picture's 2.07 M luma samples are inter-predicted.
 PU_HIST = {(64, 64): 150, (32, 32): 420, (64, 32): 60, (32, 64): 60, (32, 16): 160, (16, 32): 160, (16, 16): 900, (16, 8): 260, (8, 16): 260, (8, 8): 700, (8, 4): 120, (4, 8): 120}
 SEED = 20240
+# affine CUs of one picture: (width, height) -> count
+AFFINE_HIST = {(64, 64): 60, (32, 32): 200, (64, 32): 40, (32, 64): 40, (32, 16): 100, (16, 32): 100, (16, 16): 500}
+AFFINE_CTU, AFFINE_D = 128, 32
 
 
 class OtherBuild:
@@ -123,6 +130,30 @@ def b_picture_items(rng, luma_stride, chroma_stride, org_stride):
                 recs.append(it)
     items = np.concatenate(recs)
     return items[rng.permutation(len(items))], at, rd, wr
+
+
+def affine_items(rng, prof):
+    """luma + Cb + Cr items of every CU of AFFINE_HIST; planes 0 / 1: luma of list 0 / 1, 2 / 3: Cb, 4 / 5: Cr (offsets filled by the caller: they depend on the planes)"""
+    from vvenc_amd.hotpath import PRED_AFFINE_ITEM_DTYPE
+    recs = []
+    for (w, h), count in AFFINE_HIST.items():
+        for _ in range(count):
+            it = np.zeros(1, PRED_AFFINE_ITEM_DTYPE)
+            it["cu_w"], it["cu_h"], it["cu_x"], it["cu_y"] = w, h, int(rng.integers(0, (W - w) // w + 1)) * w, int(rng.integers(0, (H - h) // h + 1)) * h
+            it["six_param"], it["prof"] = int(rng.integers(0, 2)), prof
+            bi, first = bool(rng.integers(0, 2)), int(rng.integers(0, 2))
+            for l in (0, 1):
+                lt = rng.integers(-128, 129, 2)
+                it["cpmv"][0, l, 0] = lt
+                it["cpmv"][0, l, 1] = lt + rng.integers(-AFFINE_D * w // 16, AFFINE_D * w // 16 + 1, 2)
+                it["cpmv"][0, l, 2] = lt + rng.integers(-AFFINE_D * h // 16, AFFINE_D * h // 16 + 1, 2)
+                it["ref_plane"][0, l] = l if bi or l == first else -1
+            for comp in range(3):
+                c = it.copy()
+                c["chroma"] = 1 if comp else 0
+                c["ref_plane"] = np.where(it["ref_plane"] >= 0, it["ref_plane"] + 2 * comp, -1)
+                recs.append(c)
+    return np.concatenate(recs)
 
 
 def stats(ts):
@@ -243,6 +274,74 @@ def main():
                             "hbm_peak_fraction": round((rd + wr) / sec / HBM_PEAK, 4), "host_first_call_us": round(host_first * 1e6, 1), "host_repeated_call_us": round(host_again * 1e6, 1)}
     res["b_picture_mix_bdof"] = {"items": int(len(items)), "bdof_items": int(on.sum()), "bdof_samples": int((items["width"].astype(np.int64) * items["height"])[on].sum()), **sb,
                                  "ratio_to_plain": round(sb["median_us"] / st["median_us"], 3), "changed_samples": int((pred2 != pred).sum().item())}
+    # ---- C: the affine mix through vvhip_pred_affine_batch and, expanded into 4x4 items, through vvhip_pred_inter_batch; then with PROF
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import affine_ref as AR
+    from vvenc_amd.hotpath import PRED_ITEM_DTYPE
+    APAD = AFFINE_CTU + 16
+    aplanes = [hp.plane(y0, APAD), hp.plane(y1, APAD)] + [hp.plane(chroma_of(y, k), APAD // 2) for k in (0, 1) for y in (y0, y1)]
+    arng = np.random.default_rng(SEED + 1)
+    aff = affine_items(arng, 0)
+    sizes = (aff["cu_w"].astype(np.int64) >> aff["chroma"]) * (aff["cu_h"].astype(np.int64) >> aff["chroma"])
+    aff["dst_off"] = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    atotal = int(sizes.sum())
+    strides = [p.stride for p in aplanes]
+    for k in range(len(aff)):
+        c = int(aff[k]["chroma"])
+        for l in (0, 1):
+            if aff[k]["ref_plane"][l] >= 0:
+                aff[k]["ref_off"][l] = (int(aff[k]["cu_y"]) >> c) * strides[int(aff[k]["ref_plane"][l])] + (int(aff[k]["cu_x"]) >> c)          # (Plane.buf_ptr addresses sample (0, 0))
+    t0 = time.perf_counter()
+    ex = []
+    for k in range(len(aff)):
+        e, _, _ = AR.expand_items(aff[k], strides, W, H, AFFINE_CTU, PRED_ITEM_DTYPE)
+        e["dst_off"] += int(aff[k]["dst_off"])
+        ex.append(e)
+    ex = np.concatenate(ex)
+    expand_s = time.perf_counter() - t0
+    hpa, hpe, hpp = HotPath(), HotPath(), HotPath()
+    outs = [torch.zeros(atotal, dtype=torch.int16, device=hp.device) for _ in range(3)]
+    affp = aff.copy()
+    affp["prof"] = 1
+    fns = {"affine_batch": (hpa, lambda: hpa.pred_affine_batch(aplanes, aff, outs[0], 0, 10, W, H, AFFINE_CTU)),
+           "expanded_4x4_inter_batch": (hpe, lambda: hpe.pred_inter_batch(aplanes, ex, outs[1], 0, 10)),
+           "affine_batch_prof": (hpp, lambda: hpp.pred_affine_batch(aplanes, affp, outs[2], 0, 10, W, H, AFFINE_CTU))}
+    first_call, graphs = {}, {}
+    for name, (h, fn) in fns.items():
+        h.use_own_stream()
+        t0 = time.perf_counter(); fn(); first_call[name] = time.perf_counter() - t0
+        h.sync()
+        graphs[name] = h.graph_capture(fn)
+    a_np, e_np = outs[0].cpu().numpy(), outs[1].cpu().numpy()
+    for k in range(len(aff)):
+        c, o = int(aff[k]["chroma"]), int(aff[k]["dst_off"])
+        bw, bh = int(aff[k]["cu_w"]) >> c, int(aff[k]["cu_h"]) >> c
+        assert np.array_equal(AR.blocks_to_block(e_np[o:o + bw * bh], bw, bh), a_np[o:o + bw * bh].reshape(bh, bw)), ("the affine entry and the expanded list disagree on item", k)
+
+    def run_aff(name, reps):
+        h = fns[name][0]
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            h.graph_launch(graphs[name])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps
+    anames = list(fns)
+    atimes = {k: [] for k in anames}
+    for k in anames:
+        run_aff(k, 5)
+    for r in range(a.rounds):
+        for k in (anames if r % 2 == 0 else anames[::-1]):
+            atimes[k].append(run_aff(k, a.reps))
+    ast = {k: stats(v) for k, v in atimes.items()}
+    tiles = int(sum(max(1, (int(i["cu_w"]) >> int(i["chroma"])) * (int(i["cu_h"]) >> int(i["chroma"])) // 256) for i in aff))
+    allow = max(ast["affine_batch"]["spread"], ast["expanded_4x4_inter_batch"]["spread"]) * ast["expanded_4x4_inter_batch"]["median_us"]
+    res["affine_mix"] = {"cus": int(sum(AFFINE_HIST.values())), "items": int(len(aff)), "expanded_items": int(len(ex)), "samples": atotal, "outputs_equal": True,
+                         **{k: v for k, v in ast.items()},
+                         "condition_affine_not_slower_than_expanded_plus_spread": bool(ast["affine_batch"]["median_us"] <= ast["expanded_4x4_inter_batch"]["median_us"] + allow),
+                         "host_first_call_us": {k: round(v * 1e6, 1) for k, v in first_call.items()}, "host_expansion_ms": round(expand_s * 1e3, 1),
+                         "record_bytes": {"affine_batch": int(len(aff)) * 80, "expanded_4x4_inter_batch": int(len(ex)) * 32},
+                         "schedule_bytes": {"affine_batch": int(len(aff)) * 96 + tiles * 8 + ((tiles + 3) // 4) * 4 * 16, "expanded_4x4_inter_batch": int(len(ex)) * (48 + 8) + ((len(ex) + 63) // 64) * 4 * 16},
+                         "prof_changed_samples": int((outs[2] != outs[0]).sum().item()), "prof_ratio_to_plain": round(ast["affine_batch_prof"]["median_us"] / ast["affine_batch"]["median_us"], 3)}
     for k, v in res.items():
         print(k, json.dumps(v) if isinstance(v, dict) else v)
     if a.json:

@@ -51,6 +51,15 @@ struct vvhip_ctx
   hipStream_t  predStream = nullptr;       // the stream the schedule was uploaded on; compared only, never used as a handle
   hipEvent_t   predEvent  = nullptr;       // recorded behind every launch that reads the schedule
   bool         predEventRecorded = false;
+  // the same for vvhip_pred_affine_batch (predaffine.hip): a schedule, key, host copy and event of its own — alternating the two entries on one context evicts neither
+  void*        d_affSched = nullptr;
+  size_t       affBytes   = 0;
+  std::vector<unsigned char> affKey, affBlob;
+  size_t       affOffSubs = 0, affOffUnits = 0;
+  int          affUnits   = 0;
+  hipStream_t  affStream  = nullptr;
+  hipEvent_t   affEvent   = nullptr;
+  bool         affEventRecorded = false;
   // how the host waits for the stream (vvhip_set_blocking_sync): false = hipStreamSynchronize (the runtime's low-latency wait), true = a blocking event — the calling thread
   // sleeps, which matters when the host's cores are all busy encoding
   bool         blockingSync = false;
@@ -127,6 +136,9 @@ struct VvhipTuMx64Ops
 void vvhip_build_tr_matrix( int trType, int log2N, int16_t* out );          // host
 void vvhip_build_scan_order( int log2w, int log2h, uint32_t* out );         // host
 void vvhip_cg_size( int log2w, int log2h, int* log2CGw, int* log2CGh );     // host
+
+// XCD-aware order of a size class's workgroups (pred.hip), shared by the prediction-list entries
+std::vector<int> predBandOrder( int nGroups, int base );
 
 static inline int ilog2i( int v ) { int l = 0; while( ( 1 << ( l + 1 ) ) <= v ) l++; return l; }
 static inline bool isPow2( int v ) { return v > 0 && ( v & ( v - 1 ) ) == 0; }

@@ -252,6 +252,8 @@ void vvhip_destroy( vvhip_ctx* ctx )
   if( ctx->tuGenEvent ) ( void ) hipEventDestroy( ctx->tuGenEvent );
   if( ctx->d_predSched ) ( void ) hipFree( ctx->d_predSched );
   if( ctx->predEvent ) ( void ) hipEventDestroy( ctx->predEvent );
+  if( ctx->d_affSched ) ( void ) hipFree( ctx->d_affSched );
+  if( ctx->affEvent ) ( void ) hipEventDestroy( ctx->affEvent );
   if( ctx->d_mctfStats ) ( void ) hipFree( ctx->d_mctfStats );
   for( hipEvent_t e : ctx->mctfEv ) ( void ) hipEventDestroy( e );
   if( ctx->ownStream ) ( void ) hipStreamDestroy( ctx->ownStream );

@@ -901,6 +901,36 @@ bool InterPredOps::predictList( const Pel* const* refPlanes, int numPlanes, cons
   return true;
 }
 
+bool InterPredOps::predictAffineList( const Pel* const* refPlanes, int numPlanes, const vvhip_pred_affine_item* items, int n, int picWidth, int picHeight, int ctuSize, int bitDepth,
+                                      Pel* pred, size_t predElems, const Pel* org, Pel* resi )
+{
+  if( numPlanes < 1 || numPlanes > 16 || n < 0 || !pred || ( resi && !org ) ) return false;
+  Device& dev = Device::get();
+  auto mirrorOf = [&dev]( const Pel* p ) { Device::Found f = dev.findReference( p ); return f ? f : dev.find( p ); };
+  vvhip_me_plane table[16];
+  for( int k = 0; k < numPlanes; k++ )
+  {
+    const Device::Found f = mirrorOf( refPlanes[k] );
+    if( !f ) return false;
+    table[k].d_base = f->dOrigin + ( refPlanes[k] - f->origin ); table[k].stride = f->stride; table[k].reserved = 0;
+  }
+  const int16_t* dOrg = nullptr; int orgStride = 0;
+  if( resi )
+  {
+    const Device::Found f = mirrorOf( org );
+    if( !f ) return false;
+    dOrg = f->dOrigin + ( org - f->origin ); orgStride = f->stride;
+  }
+  if( n == 0 ) return true;
+  const size_t bytes = ( predElems * sizeof( Pel ) + 255 ) & ~( size_t ) 255;
+  int16_t* dPred = dev.staging( ( resi ? 2 : 1 ) * bytes + 256 );
+  int16_t* dResi = resi ? dPred + bytes / sizeof( Pel ) : nullptr;
+  dev.check( vvhip_pred_affine_batch( dev.ctx(), table, numPlanes, items, n, picWidth, picHeight, ctuSize, bitDepth, dPred, 0, dOrg, orgStride, dResi ), "vvhip_pred_affine_batch" );
+  if( resi ) dev.check( vvhip_download_async( dev.ctx(), resi, dResi, predElems * sizeof( Pel ) ), "affine prediction list residual" );
+  dev.check( vvhip_download( dev.ctx(), pred, dPred, predElems * sizeof( Pel ) ), "affine prediction list" );      // (waits for the stream: both copies are done)
+  return true;
+}
+
 // ------------------------------------------------------------------------------------------------ ALFOps
 namespace {
 // stages a plane with its 4-sample border compactly: returns the device pointer of sample (0,0) and the pitch

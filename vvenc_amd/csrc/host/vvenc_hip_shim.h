@@ -245,6 +245,11 @@ struct InterPredOps
   // (vvhip_pred_inter_batch_ex).
   bool predictList( const Pel* const* refPlanes, int numPlanes, const vvhip_pred_item* items, int n, int bitDepth, Pel* pred, size_t predElems, const Pel* org = nullptr, Pel* resi = nullptr,
                     const vvhip_pred_ext* ext = nullptr );
+  // The same for a list of affine CUs given by their control-point vectors (vvhip_pred_affine_batch: InterPredInterpolation::xPredAffineBlk, :1497-1839, PROF included):
+  // items: vvhip_pred_affine_item records, one per component block, ref_off / org_off = the block's own position at the picture's line pitch; picWidth / picHeight / ctuSize
+  // (luma) feed the picture clip.  Planes, outputs, residual and the return value as predictList.
+  bool predictAffineList( const Pel* const* refPlanes, int numPlanes, const vvhip_pred_affine_item* items, int n, int picWidth, int picHeight, int ctuSize, int bitDepth,
+                          Pel* pred, size_t predElems, const Pel* org = nullptr, Pel* resi = nullptr );
 };
 
 // ALF encoder statistics: whole-plane forms of AdaptiveLoopFilter::m_deriveClassificationBlk (CommonLib/AdaptiveLoopFilter.h,

@@ -21,7 +21,8 @@
 //   BDOF                      xSubPuBDOF :326-357, xPredInterBlk :822-831 + :868-901, xApplyBDOF :911-958, gradFilterCore :114-155, calcBDOFSumsCore :157-186,
 //                             xFpBiDirOptFlowCore :607-661, addBDOFAvgCore :63-86: a lane group per 16x16 / 16x8 / 8x16 unit; each list's 14-bit block goes to LDS inside its ring
 //                             of integer samples, the lanes take the gradients of their own samples, a lane pair per 4x4 unit sums the 6x6 window, the offsets come back by lane read.
-// Still the caller's: the BDOF conditions on POC distances and CU flags, BCW / explicit weighted prediction, GEO, affine / PROF.
+// Still the caller's: the BDOF conditions on POC distances and CU flags, BCW / explicit weighted prediction, GEO.  Affine CUs with PROF have an entry of their own that takes the
+// control-point vectors (vvhip_pred_affine_batch, predaffine.hip: its own kernel and its own schedule cache; the 4x4 forms here are what it is checked against).
 #include <algorithm>
 #include <string.h>
 #include "common.h"
@@ -533,7 +534,8 @@ predOneSizeKernel( const int16_t* __restrict__ ref, int refStride, const vvhip_s
 
 // XCD-aware order of a class's workgroups (as me.hip's xcdBandOrder): workgroups are dealt round-robin to the 8 XCDs, each with a private L2; workgroup base + l of the launch
 // is handed the next entry of the ( ( base + l ) % 8 )-th contiguous eighth of the class, whose entries are sorted by picture position: every L2 streams one horizontal band.
-std::vector<int> predBandOrder( int nGroups, int base )
+} // namespace
+std::vector<int> predBandOrder( int nGroups, int base )      // (shared with predaffine.hip: declared in common.h)
 {
   std::vector<int> perm( nGroups );
   const int q = ( nGroups + 7 ) / 8;
@@ -547,6 +549,7 @@ std::vector<int> predBandOrder( int nGroups, int base )
   }
   return perm;
 }
+namespace {
 
 struct Keyed { uint32_t cls; int64_t pos; int idx; };
 

@@ -27,6 +27,8 @@ PRED_ITEM_DTYPE = np.dtype([("dst_off", "<i4"), ("org_off", "<i4"), ("ref_off", 
                             ("ref_plane", "i1", (2,)), ("chroma", "u1"), ("alt_hpel", "u1")])      # vvhip_pred_item (32 bytes)
 PRED_EXT_DTYPE = np.dtype([("flags", "u1"), ("pad_dx", "i1", (2,)), ("pad_dy", "i1", (2,)), ("rsv", "u1", (3,))])      # vvhip_pred_ext (8 bytes)
 PRED_EXT_BDOF, PRED_EXT_DMVR_PAD = 1, 2
+PRED_AFFINE_ITEM_DTYPE = np.dtype([("dst_off", "<i4"), ("org_off", "<i4"), ("ref_off", "<i4", (2,)), ("cpmv", "<i4", (2, 3, 2)), ("cu_x", "<i2"), ("cu_y", "<i2"), ("cu_w", "<i2"),
+                                   ("cu_h", "<i2"), ("ref_plane", "i1", (2,)), ("chroma", "u1"), ("six_param", "u1"), ("prof", "u1"), ("rsv", "u1", (3,))])      # vvhip_pred_affine_item (80 bytes)
 
 
 def dmvr_pred_items(results, start_mv, pos, ref_planes, strides, dx, dy, bdof=True, chroma_planes=None, chroma_strides=None):
@@ -580,6 +582,16 @@ class HotPath:
             return pred
         self._ck(self.L.vvhip_pred_inter_batch(self.ctx, C.cast(tab, C.c_void_p), len(planes), it.ctypes.data_as(C.c_void_p) if it.size else None, int(it.size), bit_depth,
                                                _ptr(pred), pred_stride, org.buf_ptr if org is not None else None, org.stride if org is not None else 0, _ptr(resi)))
+        return pred
+
+    def pred_affine_batch(self, planes, items, pred, pred_stride, bit_depth, pic_w, pic_h, ctu, org=None, resi=None):
+        """inter prediction of a list of affine CUs from their control-point vectors in one launch (vvhip_pred_affine_batch): items = PRED_AFFINE_ITEM_DTYPE records, one
+        per component block (HOST array); planes, pred, pred_stride, org, resi as pred_inter_batch; pic_w / pic_h / ctu = the luma picture and CTU size of the picture clip."""
+        it = np.ascontiguousarray(items, PRED_AFFINE_ITEM_DTYPE)
+        tab = (self._MePlane * max(1, len(planes)))(*[self._MePlane(p.buf_ptr.value, p.stride, 0) for p in planes])
+        self._ck(self.L.vvhip_pred_affine_batch(self.ctx, C.cast(tab, C.c_void_p), len(planes), it.ctypes.data_as(C.c_void_p) if it.size else None, int(it.size),
+                                                int(pic_w), int(pic_h), int(ctu), bit_depth, _ptr(pred), pred_stride,
+                                                org.buf_ptr if org is not None else None, org.stride if org is not None else 0, _ptr(resi)))
         return pred
 
     def subpel_dist_batch(self, func, org, ref, d_items, n, w, h, bit_depth=10, filter_mode=0, use_alt_hpel=False, out=None):

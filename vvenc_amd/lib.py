@@ -86,6 +86,7 @@ PROTOTYPES = {
     "vvhip_interp_chroma_batch": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "vvhip_pred_inter_batch": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, vp, i32, vp]),
     "vvhip_pred_inter_batch_ex": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, i32, vp, i32, vp]),
+    "vvhip_pred_affine_batch": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp]),
     "vvhip_subpel_dist_batch": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "vvhip_mctf_apply_plane": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, C.c_double, C.c_double, vp, i32]),
     "vvhip_mctf_filter_params": (i32, [i32, i32, C.c_double, i32, vp, vp]),
