@@ -443,7 +443,9 @@ VVHIP_API int  vvhip_me_plan_info( const vvhip_me_plan* plan, int* waves_int, in
  * copy of its PREFETCHED window, not the true plane) are per-item extensions: vvhip_pred_inter_batch_ex below.  Without them this entry is exact for DMVR sub-blocks whose
  * refinement is zero and for every PU BDOF does not apply to.
  * Affine CUs with PROF have an entry of their own that takes the control-point vectors: vvhip_pred_affine_batch below.
- * NOT done here (the caller's job, as before): BCW and explicit weighted prediction; GEO blending; IBC; reference picture resampling; the chroma phases of 4:2:2 and 4:4:4.
+ * BCW's block weights and GEO's per-sample blending of two hypotheses are per-item blend records: vvhip_pred_inter_batch_blend below.
+ * NOT done here (the caller's job, as before): explicit weighted prediction (slice-level weight tables); CIIP (needs intra prediction); IBC; reference picture resampling;
+ * the chroma phases of 4:2:2 and 4:4:4.
  * ====================================================================================================================== */
 typedef struct
 {
@@ -489,6 +491,33 @@ VVHIP_API int vvhip_pred_inter_batch_ex( vvhip_ctx* ctx, const vvhip_me_plane* p
                                          const vvhip_pred_ext* ext_host /* may be NULL */, int n, int bit_depth,
                                          int16_t* d_pred, int pred_stride,
                                          const int16_t* d_org /* may be NULL */, int org_stride, int16_t* d_resi /* may be NULL */ );
+/* The same entry with a per-item blend record (blend_host: a HOST array parallel to items_host; NULL = exactly vvhip_pred_inter_batch_ex).  BCW and GEO are one arithmetic
+ * on the two 14-bit intermediates:  ClipPel( ( w0 * s0 + ( 8 - w0 ) * s1 + offset ) >> shift ), shift = max( 2, IF_INTERNAL_PREC - bitDepth ) + 3,
+ * offset = ( 1 << ( shift - 1 ) ) + ( IF_INTERNAL_OFFS << 3 ).
+ *   VVHIP_PRED_BLEND_DEFAULT : the item is what it is without a blend record (its extension record, if any, applies).
+ *   VVHIP_PRED_BLEND_BCW     : AreaBuf<Pel>::addWeightedAvg (CommonLib/Buffer.cpp:509-546, core :143-156), getBcwWeight (Rom.cpp:1150-1163): param = bcw_idx 0..4,
+ *               w1 = { -2, 3, 4, 5, 10 }[bcw_idx], w0 = 8 - w1 for the whole block.  Every size the entry takes, luma and chroma; bcw_idx 2 is exactly the default average.
+ *   VVHIP_PRED_BLEND_GEO     : InterpolationFilter::xWeightedGeoBlk (CommonLib/InterpolationFilter.cpp:1005-1064, tables Rom.cpp:1304-1382): param = geoSplitDir 0..63.
+ *               The item is a WHOLE component block of the CU: luma w, h in { 8, 16, 32, 64 } (all 16 combinations), a 4:2:0 chroma item 4..32 per side with the CU's luma
+ *               size taken as twice the item's.  ref_plane[k] / ref_off[k] / frac[k] describe partition k's hypothesis (which reference list it comes from does not matter);
+ *               both are interpolated as uni-directional hypotheses to the 14-bit intermediate (InterPrediction.cpp:441, :1001-1004) and w0 = the weight mask at the sample.
+ *               The host reduces split direction + CU size to three integers per item and the kernel derives each weight from them (no weight table or block on the device);
+ *               vvhip_get_geo_weights_host returns the same weights.
+ * A BCW or GEO item uses BOTH hypotheses.  The CU-level conditions are the caller's, as with BDOF: BCW's size rule, maxDim < 8 * minDim for GEO (EncCu.cpp:1946).
+ * Argument errors (VVHIP_E_ARG with a message naming this entry, nothing launched): unknown mode; param out of range; non-zero rsv; a BCW or GEO item with one hypothesis;
+ * a GEO size outside the set above; BCW or GEO on an item whose extension record carries VVHIP_PRED_EXT_BDOF or VVHIP_PRED_EXT_DMVR_PAD (the reference excludes both:
+ * InterPrediction.cpp:478, :975).  Everything vvhip_pred_inter_batch promises holds: order independence, both output layouts, the residual, the schedule cache — the blend
+ * array is part of the list's key, and a list with a blend array keeps a schedule of its own: alternating with vvhip_pred_inter_batch[_ex] and vvhip_pred_affine_batch on one
+ * context evicts none of the three.
+ * Still the caller's: explicit weighted prediction, CIIP, IBC.                                                                                                          */
+#define VVHIP_PRED_BLEND_DEFAULT 0   /* exactly what the item does without a blend record     */
+#define VVHIP_PRED_BLEND_BCW     1   /* param = bcw_idx 0..4                                  */
+#define VVHIP_PRED_BLEND_GEO     2   /* param = geoSplitDir 0..63                             */
+typedef struct { uint8_t mode, param, rsv[2]; } vvhip_pred_blend;   /* 4 bytes, rsv zero */
+VVHIP_API int vvhip_pred_inter_batch_blend( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host,
+                                            const vvhip_pred_ext* ext_host /* may be NULL */, const vvhip_pred_blend* blend_host /* may be NULL */, int n, int bit_depth,
+                                            int16_t* d_pred, int pred_stride,
+                                            const int16_t* d_org /* may be NULL */, int org_stride, int16_t* d_resi /* may be NULL */ );
 /* Inter prediction of a LIST of AFFINE CUs from their control-point vectors: what InterPredInterpolation::xPredAffineBlk (CommonLib/InterPrediction.cpp:1497-1839) + the
  * default weighted average produce for one component block of one affine CU, PROF included, bit-exact.  One item is one component block; the CU record is all that
  * crosses to the device — the sub-block vectors, fractions and PROF's dMv table are derived in the kernel.
@@ -541,6 +570,10 @@ VVHIP_API int vvhip_interp_chroma_batch( vvhip_ctx* ctx, const int16_t* d_ref, i
  * g_trCore* (CommonLib/RomTr.cpp:364-449) and getScanOrder (CommonLib/Rom.h:104).               */
 VVHIP_API int vvhip_get_tr_matrix_host( int tr_type, int log2_size, int16_t* host_out );
 VVHIP_API int vvhip_get_scan_order_host( int log2_w, int log2_h, uint32_t* host_out );
+/* the GEO weights w0 (0..8) of one component block as vvhip_pred_inter_batch_blend applies them: split_dir 0..63, the CU's luma size as log2 3..6 per side, chroma 0 = the
+ * luma block, 1 = a 4:2:0 chroma block ( cu_w / 2 ) x ( cu_h / 2 ); host_out takes width * height entries, row by row.  For parity checks against xWeightedGeoBlk
+ * (g_globalGeoWeights / g_weightOffset / g_angle2mirror / g_GeoParams, CommonLib/Rom.cpp:1304-1382).  Needs no device.                                              */
+VVHIP_API int vvhip_get_geo_weights_host( int split_dir, int log2_cu_w, int log2_cu_h, int chroma, int8_t* host_out );
 /* the six tap tables of a motion-search plan's refinement-stage kernels at this bit depth (8..10), 6 x 192 dwords, table = filter_mode * 2 + alt_hpel:
  * [0..127] 16 phases x 8 window taps (tap k multiplies the sample at offset k - 3) of the SECOND pass, scaled by 2^(16 - shift2), shift2 = 6 + headRoom, headRoom = 14 - bit_depth
  * (InterpolationFilter.cpp:394-400: the filtered sample is the upper half of the 32-bit sum); [128..191] 16 phases x 4 packed int16 pairs (taps K0 + 2i, K0 + 2i + 1 of the table's

@@ -15,6 +15,9 @@ C. the affine mix: seeded affine CUs AFFINE_HIST (sizes 16..64, half bi-predicte
    vvhip_pred_affine_batch, and the same CUs expanded by the host into 4x4 items (tests/affine_ref.expand_items: what a caller had to do before) through
    vvhip_pred_inter_batch of the same build, in the same rounds; the outputs are compared first.  Then the same mix with prof = 1.  Reported besides the times: the host
    time of each first call and the bytes of list records and of device schedule each path uploads (from the record sizes of pred.hip / predaffine.hip).
+D. the blend mix: seeded two-hypothesis CUs BLEND_HIST (the GEO size range 8..64, 1080p positions, luma + Cb + Cr), half of them BCW (index 0, 1, 3 or 4) and half GEO
+   (any split direction), through vvhip_pred_inter_batch_blend — and the same items as plain bi-predicted items (blend = NULL: the cost floor of these blocks) through
+   a second context, in the same rounds.  Reported: both times, their ratio, and how many samples the blend records change.
 Every variant is recorded into a launch graph once and timed as `reps` graph launches between two host clock readings that end in a device synchronise, `rounds` times, the
 variants alternating inside a round; medians, minima and the spread ( max - min ) / median are printed.  --quick: one round of few launches (for a profiler run)."""
 import argparse
@@ -37,6 +40,8 @@ SEED = 20240
 # affine CUs of one picture: (width, height) -> count
 AFFINE_HIST = {(64, 64): 60, (32, 32): 200, (64, 32): 40, (32, 64): 40, (32, 16): 100, (16, 32): 100, (16, 16): 500}
 AFFINE_CTU, AFFINE_D = 128, 32
+# two-hypothesis CUs with a blend record of one picture: (width, height) -> count
+BLEND_HIST = {(64, 64): 30, (32, 32): 90, (64, 32): 20, (32, 64): 20, (32, 16): 50, (16, 32): 50, (16, 16): 160, (16, 8): 40, (8, 16): 40, (8, 8): 100}
 
 
 class OtherBuild:
@@ -154,6 +159,32 @@ def affine_items(rng, prof):
                 c["ref_plane"] = np.where(it["ref_plane"] >= 0, it["ref_plane"] + 2 * comp, -1)
                 recs.append(c)
     return np.concatenate(recs)
+
+
+def blend_items(rng, luma_stride, chroma_stride):
+    """luma + Cb + Cr items of every CU of BLEND_HIST, all with two hypotheses; planes as b_picture_items.  -> (items, blend records, samples)"""
+    from vvenc_amd.hotpath import PRED_BLEND_BCW, PRED_BLEND_DTYPE, PRED_BLEND_GEO, PRED_ITEM_DTYPE
+    recs, bl, at = [], [], 0
+    for (w, h), count in BLEND_HIST.items():
+        for k in range(count):
+            px, py = int(rng.integers(0, (W - w) // w + 1)) * w, int(rng.integers(0, (H - h) // h + 1)) * h
+            mv = [(int(rng.integers(-128, 129)), int(rng.integers(-128, 129))) for _ in range(2)]
+            mode, param = (PRED_BLEND_BCW, int(rng.choice([0, 1, 3, 4]))) if k % 2 == 0 else (PRED_BLEND_GEO, int(rng.integers(0, 64)))
+            for comp in range(3):
+                cs = 1 if comp else 0
+                it, b = np.zeros(1, PRED_ITEM_DTYPE), np.zeros(1, PRED_BLEND_DTYPE)
+                cw, chh, cx, cy = w >> cs, h >> cs, px >> cs, py >> cs
+                it["width"], it["height"], it["chroma"], it["dst_off"] = cw, chh, cs, at
+                b["mode"], b["param"] = mode, param
+                sh, stride = 4 + cs, chroma_stride if cs else luma_stride
+                for l in (0, 1):
+                    it["ref_plane"][0, l] = 2 * comp + l
+                    it["ref_off"][0, l] = (cy + (mv[l][1] >> sh)) * stride + cx + (mv[l][0] >> sh)
+                    it["frac"][0, l] = (mv[l][0] & ((1 << sh) - 1), mv[l][1] & ((1 << sh) - 1))
+                at += cw * chh
+                recs.append(it); bl.append(b)
+    order = rng.permutation(len(recs))
+    return np.concatenate(recs)[order], np.concatenate(bl)[order], at
 
 
 def stats(ts):
@@ -342,6 +373,38 @@ def main():
                          "record_bytes": {"affine_batch": int(len(aff)) * 80, "expanded_4x4_inter_batch": int(len(ex)) * 32},
                          "schedule_bytes": {"affine_batch": int(len(aff)) * 96 + tiles * 8 + ((tiles + 3) // 4) * 4 * 16, "expanded_4x4_inter_batch": int(len(ex)) * (48 + 8) + ((len(ex) + 63) // 64) * 4 * 16},
                          "prof_changed_samples": int((outs[2] != outs[0]).sum().item()), "prof_ratio_to_plain": round(ast["affine_batch_prof"]["median_us"] / ast["affine_batch"]["median_us"], 3)}
+    # ---- D: the blend mix through vvhip_pred_inter_batch_blend, and the same items as plain bi-predicted items
+    brng = np.random.default_rng(SEED + 2)
+    bitems, bblend, btotal = blend_items(brng, luma[0].stride, chroma[0].stride)
+    hpb, hpn = HotPath(), HotPath()
+    bouts = [torch.zeros(btotal, dtype=torch.int16, device=hp.device) for _ in range(2)]
+    bfns = {"blend_batch": (hpb, lambda: hpb.pred_inter_batch(table, bitems, bouts[0], 0, 10, blend=bblend)),
+            "same_items_plain_bi": (hpn, lambda: hpn.pred_inter_batch(table, bitems, bouts[1], 0, 10))}
+    bgraphs, bfirst = {}, {}
+    for name, (h, fn) in bfns.items():
+        h.use_own_stream()
+        t0 = time.perf_counter(); fn(); bfirst[name] = time.perf_counter() - t0
+        h.sync()
+        bgraphs[name] = h.graph_capture(fn)
+
+    def run_blend(name, reps):
+        h = bfns[name][0]
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            h.graph_launch(bgraphs[name])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps
+    bnames = list(bfns)
+    btimes = {k: [] for k in bnames}
+    for k in bnames:
+        run_blend(k, 5)
+    for r in range(a.rounds):
+        for k in (bnames if r % 2 == 0 else bnames[::-1]):
+            btimes[k].append(run_blend(k, a.reps))
+    bst = {k: stats(v) for k, v in btimes.items()}
+    res["blend_mix"] = {"cus": int(sum(BLEND_HIST.values())), "items": int(len(bitems)), "bcw_items": int((bblend["mode"] == 1).sum()), "geo_items": int((bblend["mode"] == 2).sum()),
+                        "samples": int(btotal), **bst, "ratio_to_plain": round(bst["blend_batch"]["median_us"] / bst["same_items_plain_bi"]["median_us"], 3),
+                        "changed_samples": int((bouts[0] != bouts[1]).sum().item()), "host_first_call_us": {k: round(v * 1e6, 1) for k, v in bfirst.items()}}
     for k, v in res.items():
         print(k, json.dumps(v) if isinstance(v, dict) else v)
     if a.json:

@@ -41,16 +41,21 @@ struct vvhip_ctx
   hipEvent_t   tuGenEvent  = nullptr;      // recorded behind every launch that reads the table: a caller that switches streams orders the new stream behind it
   bool         tuGenEventRecorded = false;
   // device copy of the schedule of vvhip_pred_inter_batch (pred.hip), the caller's list it was derived from (items + plane table: a list that is run again is neither sorted
-  // nor uploaded again) and the host copy the asynchronous upload reads
-  void*        d_predSched = nullptr;
-  size_t       predBytes  = 0;
-  std::vector<unsigned char> predKey, predBlob;
-  size_t       predOffSubs = 0, predOffUnits = 0;
-  int          predUnits  = 0, predLdsPerWave = 0;
-  int          predUnitsEx = 0, predLdsPerWaveEx = 0;      // the units of items with an extension (BDOF, DMVR's padded reference): behind the plain units, a kernel of their own
-  hipStream_t  predStream = nullptr;       // the stream the schedule was uploaded on; compared only, never used as a handle
-  hipEvent_t   predEvent  = nullptr;       // recorded behind every launch that reads the schedule
-  bool         predEventRecorded = false;
+  // nor uploaded again) and the host copy the asynchronous upload reads.  [0]: vvhip_pred_inter_batch[_ex]; [1]: vvhip_pred_inter_batch_blend called with a blend array —
+  // a schedule, key, host copy and event of its own, so that alternating the entries on one context evicts neither
+  struct PredSched
+  {
+    void*        d_sched   = nullptr;
+    size_t       bytes     = 0;
+    std::vector<unsigned char> key, blob;
+    size_t       offSubs   = 0, offUnits = 0, offBlend = 0;
+    int          units     = 0, ldsPerWave = 0;
+    int          unitsEx   = 0, ldsPerWaveEx = 0;          // the units of items with an extension (BDOF, DMVR's padded reference): behind the plain units, a kernel of their own
+    int          unitsBlend = 0, ldsPerWaveBlend = 0;      // the units of BCW / GEO items: behind those, a kernel of their own; their records sit at offBlend
+    hipStream_t  stream    = nullptr;      // the stream the schedule was uploaded on; compared only, never used as a handle
+    hipEvent_t   event     = nullptr;      // recorded behind every launch that reads the schedule
+    bool         eventRecorded = false;
+  } predSched[2];
   // the same for vvhip_pred_affine_batch (predaffine.hip): a schedule, key, host copy and event of its own — alternating the two entries on one context evicts neither
   void*        d_affSched = nullptr;
   size_t       affBytes   = 0;
@@ -142,6 +147,16 @@ std::vector<int> predBandOrder( int nGroups, int base );
 
 static inline int ilog2i( int v ) { int l = 0; while( ( 1 << ( l + 1 ) ) <= v ) l++; return l; }
 static inline bool isPow2( int v ) { return v > 0 && ( v & ( v - 1 ) ) == 0; }
+
+// ---- blending two hypotheses with weights w0 + w1 = 8 (pred.hip: BCW, GEO) --------------------------------------------------
+// The weight of hypothesis 0 at sample ( x, y ) of a component block is a clamped line: a BCW block has a = b = 0, c = 8 * w0 and lo = hi = w0; a GEO block has
+// lo = 0, hi = 8 and the line of its split direction through the 112 x 112 weight mask, with the CU's offset into the mask, the mirror and the component's scale folded
+// into ( a, b, c ) by the host (g_globalGeoWeights is Clip3( 0, 8, ( A * mx + B * my + C ) >> 3 ): Rom.cpp:1320-1342, read at InterpolationFilter.cpp:1024-1062).
+static inline __host__ __device__ int vvhipBlendW0( int a, int b, int c, int lo, int hi, int x, int y )
+{
+  const int w = ( a * x + b * y + c ) >> 3;
+  return w < lo ? lo : ( w > hi ? hi : w );
+}
 
 // ---- cross-lane helpers (device) ----------------------------------------------------------------------------------------
 // Sum over aligned groups of G (2..64, power of two) consecutive lanes using DPP only (no LDS crossbar traffic): quad_perm

@@ -250,8 +250,11 @@ void vvhip_destroy( vvhip_ctx* ctx )
   if( ctx->d_tuGen ) ( void ) hipFree( ctx->d_tuGen );
   if( ctx->syncEvent ) ( void ) hipEventDestroy( ctx->syncEvent );
   if( ctx->tuGenEvent ) ( void ) hipEventDestroy( ctx->tuGenEvent );
-  if( ctx->d_predSched ) ( void ) hipFree( ctx->d_predSched );
-  if( ctx->predEvent ) ( void ) hipEventDestroy( ctx->predEvent );
+  for( vvhip_ctx::PredSched& S : ctx->predSched )
+  {
+    if( S.d_sched ) ( void ) hipFree( S.d_sched );
+    if( S.event ) ( void ) hipEventDestroy( S.event );
+  }
   if( ctx->d_affSched ) ( void ) hipFree( ctx->d_affSched );
   if( ctx->affEvent ) ( void ) hipEventDestroy( ctx->affEvent );
   if( ctx->d_mctfStats ) ( void ) hipFree( ctx->d_mctfStats );

@@ -871,7 +871,7 @@ bool DMVROps::refineCu( const Pel* ref0, int stride0, int fx0, int fy0, const Pe
 
 // ------------------------------------------------------------------------------------------------ InterPredOps
 bool InterPredOps::predictList( const Pel* const* refPlanes, int numPlanes, const vvhip_pred_item* items, int n, int bitDepth, Pel* pred, size_t predElems, const Pel* org, Pel* resi,
-                                const vvhip_pred_ext* ext )
+                                const vvhip_pred_ext* ext, const vvhip_pred_blend* blend )
 {
   if( numPlanes < 1 || numPlanes > 16 || n < 0 || !pred || ( resi && !org ) ) return false;
   Device& dev = Device::get();
@@ -894,8 +894,9 @@ bool InterPredOps::predictList( const Pel* const* refPlanes, int numPlanes, cons
   const size_t bytes = ( predElems * sizeof( Pel ) + 255 ) & ~( size_t ) 255;
   int16_t* dPred = dev.staging( ( resi ? 2 : 1 ) * bytes + 256 );
   int16_t* dResi = resi ? dPred + bytes / sizeof( Pel ) : nullptr;
-  if( ext ) dev.check( vvhip_pred_inter_batch_ex( dev.ctx(), table, numPlanes, items, ext, n, bitDepth, dPred, 0, dOrg, orgStride, dResi ), "vvhip_pred_inter_batch_ex" );
-  else      dev.check( vvhip_pred_inter_batch( dev.ctx(), table, numPlanes, items, n, bitDepth, dPred, 0, dOrg, orgStride, dResi ), "vvhip_pred_inter_batch" );
+  if( blend ) dev.check( vvhip_pred_inter_batch_blend( dev.ctx(), table, numPlanes, items, ext, blend, n, bitDepth, dPred, 0, dOrg, orgStride, dResi ), "vvhip_pred_inter_batch_blend" );
+  else if( ext ) dev.check( vvhip_pred_inter_batch_ex( dev.ctx(), table, numPlanes, items, ext, n, bitDepth, dPred, 0, dOrg, orgStride, dResi ), "vvhip_pred_inter_batch_ex" );
+  else dev.check( vvhip_pred_inter_batch( dev.ctx(), table, numPlanes, items, n, bitDepth, dPred, 0, dOrg, orgStride, dResi ), "vvhip_pred_inter_batch" );
   if( resi ) dev.check( vvhip_download_async( dev.ctx(), resi, dResi, predElems * sizeof( Pel ) ), "prediction list residual" );
   dev.check( vvhip_download( dev.ctx(), pred, dPred, predElems * sizeof( Pel ) ), "prediction list" );      // (waits for the stream: both copies are done)
   return true;

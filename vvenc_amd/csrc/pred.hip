@@ -21,7 +21,13 @@
 //   BDOF                      xSubPuBDOF :326-357, xPredInterBlk :822-831 + :868-901, xApplyBDOF :911-958, gradFilterCore :114-155, calcBDOFSumsCore :157-186,
 //                             xFpBiDirOptFlowCore :607-661, addBDOFAvgCore :63-86: a lane group per 16x16 / 16x8 / 8x16 unit; each list's 14-bit block goes to LDS inside its ring
 //                             of integer samples, the lanes take the gradients of their own samples, a lane pair per 4x4 unit sums the 6x6 window, the offsets come back by lane read.
-// Still the caller's: the BDOF conditions on POC distances and CU flags, BCW / explicit weighted prediction, GEO.  Affine CUs with PROF have an entry of their own that takes the
+// Items with a blend record (vvhip_pred_inter_batch_blend) run in predListBlendKernel, the same body with another combine step: both hypotheses go to the 14-bit block and
+//   ClipPel( ( w0 * s0 + ( 8 - w0 ) * s1 + offset ) >> shift ), shift = headroom + 3, offset = ( 1 << ( shift - 1 ) ) + ( IF_INTERNAL_OFFS << 3 )
+//   BCW   AreaBuf<Pel>::addWeightedAvg CommonLib/Buffer.cpp:509-546 (core :143-156), getBcwWeight Rom.cpp:1150-1163: w0 = 8 - { -2, 3, 4, 5, 10 }[bcw_idx] for the whole block
+//   GEO   InterpolationFilter::xWeightedGeoBlk CommonLib/InterpolationFilter.cpp:1005-1064, tables Rom.cpp:1304-1382: w0 per sample, a clamped line in ( x, y ) whose three
+//         integers the host derives from the split direction and the CU size (geoLine below; vvhipBlendW0 in common.h) — no weight table and no weight block on the device.
+// Still the caller's: the BDOF conditions on POC distances and CU flags, the CU-level conditions of BCW and GEO, explicit weighted prediction (slice-level weight tables),
+// CIIP (needs intra prediction), IBC.  Affine CUs with PROF have an entry of their own that takes the
 // control-point vectors (vvhip_pred_affine_batch, predaffine.hip: its own kernel and its own schedule cache; the 4x4 forms here are what it is checked against).
 #include <algorithm>
 #include <string.h>
@@ -52,8 +58,9 @@ struct __attribute__( ( aligned( 16 ) ) ) PredDev      // one prediction item wi
   uint8_t alt, pad[3];           // extension forms: pad[0] = flags, pad[1 + l] = ( pad_dx[l] + 2 ) | ( pad_dy[l] + 2 ) << 4
 };
 struct PredSub  { int32_t item; int16_t x0, y0; };      // one tile of an item
+struct PredBlendDev { int32_t a, b, c; int16_t lo, hi; };      // w0( x, y ) of a BCW / GEO item (vvhipBlendW0); parallel to the items, read by predListBlendKernel only
 struct PredUnit { int32_t firstSub; int16_t nSub, tw, th; uint8_t kind, log2Lanes, log2SegsRow, pad[3]; };      // what one wave does (pad[0]: the extension flags of its class)
-static_assert( sizeof( PredDev ) == 48 && sizeof( PredSub ) == 8 && sizeof( PredUnit ) == 16, "schedule records" );
+static_assert( sizeof( PredDev ) == 48 && sizeof( PredSub ) == 8 && sizeof( PredUnit ) == 16 && sizeof( PredBlendDev ) == 16, "schedule records" );
 
 // kernel forms: samples per lane (a "segment": SEG horizontally adjacent samples) x taps per pass
 enum { KIND_L8 = 0, KIND_L4 = 1, KIND_C8 = 2, KIND_C4 = 3, KIND_C2 = 4 };
@@ -97,6 +104,8 @@ struct Lane
   bool bdof, clamp;
   int cx0[2], cx1[2], cy0[2], cy1[2];
   int16_t* ext;
+  // blend form only (predBody<.., FORM_BLEND>): the weight line of the item
+  int ba, bb, bc, blo, bhi;
 };
 
 #define PRED_WAVE_SYNC() { __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" ); __builtin_amdgcn_wave_barrier(); }
@@ -137,10 +146,13 @@ __host__ __device__ inline int bdofElems( int tw, int th ) { return bdofRingElem
 
 __device__ __forceinline__ int clampi( int v, int lo, int hi ) { return v < lo ? lo : ( v > hi ? hi : v ); }
 
-// EX = false: the forms of vvhip_pred_inter_batch.  EX = true adds, per unit of the schedule, the DMVR clamp in the window staging and the BDOF form of the average.
-template<int SEG, int NT, bool EX = false>
+// FORM_PLAIN: the forms of vvhip_pred_inter_batch.  FORM_EX adds, per unit of the schedule, the DMVR clamp in the window staging and the BDOF form of the average.
+// FORM_BLEND replaces the average by the weighted one of BCW / GEO (both hypotheses present: the host checks it).
+enum { FORM_PLAIN = 0, FORM_EX = 1, FORM_BLEND = 2 };
+template<int SEG, int NT, int FORM = FORM_PLAIN>
 __device__ __forceinline__ void predBody( const Lane& L, int tw, int th, int log2SegsRow, int lanes, int bitDepth )
 {
+  constexpr bool EX = FORM == FORM_EX;
   constexpr int ND = ( SEG + NT ) / 2 + 1;              // dwords that hold a segment's SEG + NT - 1 window samples at either alignment
   const int hr = 14 - bitDepth > 2 ? 14 - bitDepth : 2, maxv = ( 1 << bitDepth ) - 1;
   const int pitch = tw + NT + 2, segsRow = 1 << log2SegsRow;
@@ -355,6 +367,17 @@ __device__ __forceinline__ void predBody( const Lane& L, int tw, int th, int log
   }
   if( !L.on ) return;
   if( EX && SEG == 8 && NT == 8 && L.bdof ) {}
+  else if( FORM == FORM_BLEND )      // each lane's SEG adjacent samples: w0 constant (BCW) or stepping along the row (GEO), 32-bit (|10 * s| < 2^19)
+  {
+    const int sn = hr + 3, off = ( 1 << ( sn - 1 ) ) + ( 8192 << 3 );
+#pragma unroll
+    for( int j = 0; j < SEG; j++ )
+    {
+      const int w0 = vvhipBlendW0( L.ba, L.bb, L.bc, L.blo, L.bhi, L.x0 + xs + j, L.y0 + y );
+      const int v = ( w0 * first[j] + ( 8 - w0 ) * acc[j] + off ) >> sn;
+      acc[j] = v < 0 ? 0 : ( v > maxv ? maxv : v );
+    }
+  }
   else if( L.mode == MODE_BI )      // addAvg: ClipPel( ( a + b + offset ) >> shiftNum ), shiftNum = headroom + 1, offset = ( 1 << headroom ) + 2 * IF_INTERNAL_OFFS (Buffer.cpp:129-141, :549-575)
   {
     const int sn = hr + 1, off = ( 1 << hr ) + 2 * 8192;
@@ -415,11 +438,23 @@ __device__ __forceinline__ void predDispatchEx( int kind, const Lane& L, int tw,
 {
   switch( kind )      // wave-uniform
   {
-  case KIND_L8: predBody<8, 8, true>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
-  case KIND_L4: predBody<4, 8, true>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
-  case KIND_C8: predBody<8, 4, true>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
-  case KIND_C4: predBody<4, 4, true>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
-  default:      predBody<2, 4, true>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_L8: predBody<8, 8, FORM_EX>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_L4: predBody<4, 8, FORM_EX>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_C8: predBody<8, 4, FORM_EX>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_C4: predBody<4, 4, FORM_EX>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  default:      predBody<2, 4, FORM_EX>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  }
+}
+
+__device__ __forceinline__ void predDispatchBlend( int kind, const Lane& L, int tw, int th, int log2SegsRow, int lanes, int bitDepth )
+{
+  switch( kind )      // wave-uniform
+  {
+  case KIND_L8: predBody<8, 8, FORM_BLEND>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_L4: predBody<4, 8, FORM_BLEND>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_C8: predBody<8, 4, FORM_BLEND>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_C4: predBody<4, 4, FORM_BLEND>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  default:      predBody<2, 4, FORM_BLEND>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
   }
 }
 
@@ -506,6 +541,38 @@ predListExKernel( PredArgs a )
   predDispatchEx( u.kind, L, u.tw, u.th, u.log2SegsRow, lanes, a.bitDepth );
 }
 
+// the units of BCW / GEO items (vvhip_pred_inter_batch_blend): both hypotheses to the 14-bit block, then the weighted average with the item's weight line.
+// A kernel of its own, as the extension forms: the other forms keep their registers.
+__global__ void __launch_bounds__( 256 )
+predListBlendKernel( PredArgs a, const PredBlendDev* __restrict__ blend )
+{
+  extern __shared__ __attribute__( ( aligned( 16 ) ) ) int16_t sPred[];
+  const int wave = __builtin_amdgcn_readfirstlane( ( int ) ( threadIdx.x >> 6 ) ), lane = threadIdx.x & 63;
+  const int ui = ( int ) blockIdx.x * 4 + wave;
+  if( ui >= a.nUnits ) return;
+  const PredUnit u = a.units[ui];
+  if( u.nSub == 0 ) return;
+  const int nt = u.kind <= KIND_L4 ? 8 : 4, lanes = 1 << u.log2Lanes, si = lane >> u.log2Lanes;
+  Lane L;
+  L.on = si < u.nSub;
+  L.lis = lane & ( lanes - 1 );
+  L.win = sPred + ( size_t ) wave * a.ldsPerWave + ( size_t ) si * subElems( u.tw, u.th, nt );
+  L.tmp = L.win + winElems( u.tw, u.th, nt );
+  const PredSub s = a.subs[u.firstSub + ( L.on ? si : 0 )];
+  const PredDev it = a.items[s.item];
+  const PredBlendDev bl = blend[s.item];
+  L.ref[0] = it.ref[0]; L.ref[1] = it.ref[1]; L.stride[0] = it.stride[0]; L.stride[1] = it.stride[1];
+  L.fx[0] = it.frac[0][0]; L.fy[0] = it.frac[0][1]; L.fx[1] = it.frac[1][0]; L.fy[1] = it.frac[1][1];
+  L.w = it.w; L.h = it.h; L.alt = it.alt; L.x0 = s.x0; L.y0 = s.y0;
+  L.mode = MODE_BI;
+  L.ba = bl.a; L.bb = bl.b; L.bc = bl.c; L.blo = bl.lo; L.bhi = bl.hi;
+  L.dstPitch = a.predStride ? a.predStride : it.w;
+  L.dst = a.pred + it.dstOff;
+  L.org = a.org ? a.org + it.orgOff : nullptr; L.orgPitch = a.orgStride;
+  L.res = a.resi ? a.resi + it.dstOff : nullptr; L.resPitch = L.dstPitch;
+  predDispatchBlend( u.kind, L, u.tw, u.th, u.log2SegsRow, lanes, a.bitDepth );
+}
+
 // one block size per call, items on the device (the chroma twin of vvhip_interp_luma_batch): tile g of the launch is tile g % tilesPerItem of item g / tilesPerItem
 __global__ void __launch_bounds__( 256 )
 predOneSizeKernel( const int16_t* __restrict__ ref, int refStride, const vvhip_subpel_item* __restrict__ items, int n, int w, int h, int bitDepth, int rndRes,
@@ -553,12 +620,46 @@ namespace {
 
 struct Keyed { uint32_t cls; int64_t pos; int idx; };
 
+// ---- GEO: split direction + CU size -> the weight line of one component block (host) ----
+// The reference reads g_globalGeoWeights[mask][my * 112 + mx] with mx = offX + X ( 111 - offX - X under mirror 1 ), my = offY + Y ( 111 - offY - Y under mirror 2 ),
+// ( X, Y ) = ( x, y ) << scale (InterpolationFilter.cpp:1024-1062); the mask entry is Clip3( 0, 8, ( 2 Dx mx + 2 Dy my + 36 - 111 ( Dx + Dy ) ) >> 3 ) with
+// Dx = g_Dis[angle], Dy = g_Dis[angle + 8] of the mask's own angle (Rom.cpp:1320-1342: sample positions 2 ( m + 8 ) + 1, rho = 128 ( Dx + Dy ), + 32 + 4).
+const int8_t kGeoAngle2Mask[32]   = { 0, -1, 1, 2, 3, 4, -1, -1, 5, -1, -1, 4, 3, 2, 1, -1, 0, -1, 1, 2, 3, 4, -1, -1, 5, -1, -1, 4, 3, 2, 1, -1 };
+const int8_t kGeoDis[32]          = { 8, 8, 8, 8, 4, 4, 2, 1, 0, -1, -2, -4, -4, -8, -8, -8, -8, -8, -8, -8, -4, -4, -2, -1, 0, 1, 2, 4, 4, 8, 8, 8 };
+const int8_t kGeoAngle2Mirror[32] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 2, 2, 2, 2 };
+const int8_t kGeoMaskAngle[6]     = { 0, 2, 3, 4, 5, 8 };      // the angle whose line a prestored mask holds
+void geoLine( int splitDir, int log2CuW, int log2CuH, int chroma, PredBlendDev& o )
+{
+  int angle = 0, distance = 0, mode = 0;      // g_GeoParams (Rom.cpp:1306-1319)
+  for( int ai = 0; ai < 32; ai++ ) for( int di = 0; di < 4; di++ )
+  {
+    if( ( di == 0 && ai >= 16 ) || ( ( di == 2 || di == 0 ) && ( kGeoAngle2Mask[ai] == 0 || kGeoAngle2Mask[ai] == 5 ) ) || kGeoAngle2Mask[ai] == -1 ) continue;
+    if( mode++ == splitDir ) { angle = ai; distance = di; }
+  }
+  const int W = 1 << log2CuW, H = 1 << log2CuH;      // g_weightOffset (:1344-1370)
+  int offX = ( 112 - W ) >> 1, offY = ( 112 - H ) >> 1;
+  if( distance > 0 )
+  {
+    if( angle % 16 == 8 || ( angle % 16 != 0 && H >= W ) ) offY += angle < 16 ? ( distance * H ) >> 3 : -( ( distance * H ) >> 3 );
+    else offX += angle < 16 ? ( distance * W ) >> 3 : -( ( distance * W ) >> 3 );
+  }
+  const int base = kGeoMaskAngle[kGeoAngle2Mask[angle]], Dx = kGeoDis[base], Dy = kGeoDis[base + 8];
+  const int A = 2 * Dx, B = 2 * Dy, C = 36 - 111 * ( Dx + Dy ), mirror = kGeoAngle2Mirror[angle];
+  const int sx = mirror == 1 ? -1 : 1, sy = mirror == 2 ? -1 : 1;
+  o.a = sx * A * ( 1 << chroma ); o.b = sy * B * ( 1 << chroma );
+  o.c = C + A * ( mirror == 1 ? 111 - offX : offX ) + B * ( mirror == 2 ? 111 - offY : offY );
+  o.lo = 0; o.hi = 8;
+}
+const int8_t kBcwW1[5] = { -2, 3, 4, 5, 10 };      // g_BcwWeights (Rom.cpp:1152)
+
 // validates the list, derives the schedule and uploads it; on success the context's key names the list (items + plane table) the device copy belongs to
-int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host, int n, std::vector<unsigned char>& key )
+int predBuildSchedule( vvhip_ctx* ctx, vvhip_ctx::PredSched& S, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host,
+                       const vvhip_pred_blend* blend_host, int n, std::vector<unsigned char>& key )
 {
   // ---- validation + plane table resolved; nothing is launched when any item is unsupported
   std::vector<PredDev> dev( n );
   std::vector<Keyed> order( n );
+  std::vector<PredBlendDev> blendDev( blend_host ? n : 0 );
   for( int i = 0; i < n; i++ )
   {
     const vvhip_pred_item& it = items_host[i];
@@ -608,9 +709,38 @@ int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_
       }
       d.pad[0] = ( uint8_t ) flags;
     }
-    // size class: the most samples first (their waves run longest), then shape, component and uni / bi — a wave never mixes classes; inside a class picture order
+    // ---- the blend record: BCW (any size) or GEO (a whole component block of a CU 8..64 x 8..64); both hypotheses, no BDOF / DMVR (InterPrediction.cpp:478, :975)
     const bool bi = it.ref_plane[0] >= 0 && it.ref_plane[1] >= 0;
-    order[i].cls = ( ( uint32_t ) ( 14 - ilog2i( it.width ) - ilog2i( it.height ) ) << 8 ) | ( ( uint32_t ) ilog2i( it.width ) << 4 ) | ( flags << 2 ) | ( it.chroma ? 2u : 0u ) | ( bi ? 1u : 0u );
+    uint32_t blended = 0;
+    if( blend_host )
+    {
+      const vvhip_pred_blend& b = blend_host[i];
+      memset( &blendDev[i], 0, sizeof( PredBlendDev ) );
+      if( b.mode > VVHIP_PRED_BLEND_GEO || b.rsv[0] || b.rsv[1] )
+        return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_blend: item %d: unknown blend mode %d or non-zero reserved bytes", i, b.mode );
+      if( b.mode != VVHIP_PRED_BLEND_DEFAULT )
+      {
+        const char* tool = b.mode == VVHIP_PRED_BLEND_BCW ? "BCW" : "GEO";
+        if( b.param > ( b.mode == VVHIP_PRED_BLEND_BCW ? 4 : 63 ) ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_blend: item %d: %s parameter %d out of range", i, tool, b.param );
+        if( !bi ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_blend: item %d: %s needs both hypotheses", i, tool );
+        if( flags ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_blend: item %d: %s excludes BDOF and DMVR's padded reference", i, tool );
+        if( b.mode == VVHIP_PRED_BLEND_BCW )
+        {
+          const int w0 = 8 - kBcwW1[b.param];
+          blendDev[i].c = 8 * w0; blendDev[i].lo = blendDev[i].hi = ( int16_t ) w0;
+        }
+        else
+        {
+          const int lo = it.chroma ? 4 : 8, hi = it.chroma ? 32 : 64;
+          if( it.width < lo || it.height < lo || it.width > hi || it.height > hi )
+            return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_blend: item %d: GEO on a %s block %dx%d (the component block of a CU 8..64 x 8..64)", i, it.chroma ? "chroma" : "luma", it.width, it.height );
+          geoLine( b.param, ilog2i( it.width ) + it.chroma, ilog2i( it.height ) + it.chroma, it.chroma, blendDev[i] );
+        }
+        blended = 1;
+      }
+    }
+    // size class: the most samples first (their waves run longest), then shape, form, component and uni / bi — a wave never mixes classes; inside a class picture order
+    order[i].cls = ( ( uint32_t ) ( 14 - ilog2i( it.width ) - ilog2i( it.height ) ) << 9 ) | ( ( uint32_t ) ilog2i( it.width ) << 5 ) | ( blended << 4 ) | ( flags << 2 ) | ( it.chroma ? 2u : 0u ) | ( bi ? 1u : 0u );
     const int l0 = it.ref_plane[0] >= 0 ? 0 : 1;
     order[i].pos = ( ( int64_t ) it.ref_off[l0] << 5 ) | ( uint32_t ) ( it.ref_plane[l0] & 31 );
     order[i].idx = i;
@@ -620,14 +750,15 @@ int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_
   // ---- schedule: per class the tiles in picture order, 64 lanes' worth per wave, four waves per workgroup, workgroups dealt to the XCDs in bands
   //      classes with an extension flag go to a list of their own, which predListExKernel runs; a BDOF block is cut into its 16x16 / 16x8 / 8x16 units (xSubPuBDOF :326-357)
   std::vector<PredSub> subs;
-  std::vector<PredUnit> unitsPlain, unitsEx;
-  int ldsPerWave = 0, ldsPerWaveEx = 0;
+  std::vector<PredUnit> unitsPlain, unitsEx, unitsBlend;
+  int ldsPerWave = 0, ldsPerWaveEx = 0, ldsPerWaveBlend = 0;
   for( int c0 = 0; c0 < n; )
   {
     int c1 = c0; while( c1 < n && order[c1].cls == order[c0].cls ) c1++;
     const vvhip_pred_item& f = items_host[order[c0].idx];
     const uint32_t flags = ( order[c0].cls >> 2 ) & 3u;
-    std::vector<PredUnit>& units = flags ? unitsEx : unitsPlain;
+    const bool blended = ( order[c0].cls >> 4 ) & 1u;
+    std::vector<PredUnit>& units = blended ? unitsBlend : flags ? unitsEx : unitsPlain;
     TileShape ts = tileShape( f.width, f.height, f.chroma != 0 );
     if( flags & VVHIP_PRED_EXT_BDOF )
     {
@@ -635,7 +766,8 @@ int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_
       ts.log2SegsRow = ilog2i( ts.tw / 8 ); ts.log2Lanes = ts.log2SegsRow + ilog2i( ts.th );
     }
     const int subsPerWave = 64 >> ts.log2Lanes, nt = tapsOfKind( ts.kind );
-    if( flags ) ldsPerWaveEx = std::max( ldsPerWaveEx, subsPerWave * ( subElems( ts.tw, ts.th, nt ) + ( ( flags & VVHIP_PRED_EXT_BDOF ) ? bdofElems( ts.tw, ts.th ) : 0 ) ) );
+    if( blended ) ldsPerWaveBlend = std::max( ldsPerWaveBlend, subsPerWave * subElems( ts.tw, ts.th, nt ) );
+    else if( flags ) ldsPerWaveEx = std::max( ldsPerWaveEx, subsPerWave * ( subElems( ts.tw, ts.th, nt ) + ( ( flags & VVHIP_PRED_EXT_BDOF ) ? bdofElems( ts.tw, ts.th ) : 0 ) ) );
     else ldsPerWave = std::max( ldsPerWave, subsPerWave * subElems( ts.tw, ts.th, nt ) );
     const size_t firstSub = subs.size();
     for( int k = c0; k < c1; k++ )
@@ -654,33 +786,37 @@ int predBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_
   }
 
   // ---- device copy of the schedule: grow-only; the host copy stays alive as the source of the asynchronous upload
-  std::vector<PredUnit> units( unitsPlain );      // one table: the plain units, then the units of the extension kernel
+  std::vector<PredUnit> units( unitsPlain );      // one table: the plain units, then the units of the extension kernel, then those of the blend kernel
   units.insert( units.end(), unitsEx.begin(), unitsEx.end() );
-  const size_t bItems = ( dev.size() * sizeof( PredDev ) + 255 ) & ~( size_t ) 255, bSubs = ( subs.size() * sizeof( PredSub ) + 255 ) & ~( size_t ) 255, bUnits = units.size() * sizeof( PredUnit );
-  if( ctx->predEventRecorded ) VVHIP_CHECK_HIP( ctx, hipEventSynchronize( ctx->predEvent ) );      // the last launch that reads the old schedule, whatever stream it went to
-  ctx->predKey.clear();
-  if( bItems + bSubs + bUnits > ctx->predBytes )
+  units.insert( units.end(), unitsBlend.begin(), unitsBlend.end() );
+  const size_t bItems = ( dev.size() * sizeof( PredDev ) + 255 ) & ~( size_t ) 255, bSubs = ( subs.size() * sizeof( PredSub ) + 255 ) & ~( size_t ) 255;
+  const size_t bUnits = ( units.size() * sizeof( PredUnit ) + 255 ) & ~( size_t ) 255, bBlend = blendDev.size() * sizeof( PredBlendDev ), bAll = bItems + bSubs + bUnits + bBlend;
+  if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipEventSynchronize( S.event ) );      // the last launch that reads the old schedule, whatever stream it went to
+  S.key.clear();
+  if( bAll > S.bytes )
   {
-    if( ctx->d_predSched ) ( void ) hipFree( ctx->d_predSched );
-    ctx->d_predSched = nullptr; ctx->predBytes = 0;
-    const size_t want = ( bItems + bSubs + bUnits ) + ( bItems + bSubs + bUnits ) / 4;
-    VVHIP_CHECK_HIP( ctx, hipMalloc( &ctx->d_predSched, want ) );
-    ctx->predBytes = want;
+    if( S.d_sched ) ( void ) hipFree( S.d_sched );
+    S.d_sched = nullptr; S.bytes = 0;
+    const size_t want = bAll + bAll / 4;
+    VVHIP_CHECK_HIP( ctx, hipMalloc( &S.d_sched, want ) );
+    S.bytes = want;
   }
-  ctx->predBlob.assign( bItems + bSubs + bUnits, 0 );
-  memcpy( ctx->predBlob.data(), dev.data(), dev.size() * sizeof( PredDev ) );
-  memcpy( ctx->predBlob.data() + bItems, subs.data(), subs.size() * sizeof( PredSub ) );
-  memcpy( ctx->predBlob.data() + bItems + bSubs, units.data(), bUnits );
-  VVHIP_CHECK_HIP( ctx, hipMemcpyAsync( ctx->d_predSched, ctx->predBlob.data(), ctx->predBlob.size(), hipMemcpyHostToDevice, ctx->stream ) );
-  ctx->predStream = ctx->stream;
-  ctx->predOffSubs = bItems; ctx->predOffUnits = bItems + bSubs; ctx->predUnits = ( int ) unitsPlain.size(); ctx->predLdsPerWave = ldsPerWave;
-  ctx->predUnitsEx = ( int ) unitsEx.size(); ctx->predLdsPerWaveEx = ldsPerWaveEx;
-  ctx->predKey.swap( key );
+  S.blob.assign( bAll, 0 );
+  memcpy( S.blob.data(), dev.data(), dev.size() * sizeof( PredDev ) );
+  memcpy( S.blob.data() + bItems, subs.data(), subs.size() * sizeof( PredSub ) );
+  memcpy( S.blob.data() + bItems + bSubs, units.data(), units.size() * sizeof( PredUnit ) );
+  if( bBlend ) memcpy( S.blob.data() + bItems + bSubs + bUnits, blendDev.data(), bBlend );
+  VVHIP_CHECK_HIP( ctx, hipMemcpyAsync( S.d_sched, S.blob.data(), S.blob.size(), hipMemcpyHostToDevice, ctx->stream ) );
+  S.stream = ctx->stream;
+  S.offSubs = bItems; S.offUnits = bItems + bSubs; S.offBlend = bItems + bSubs + bUnits; S.units = ( int ) unitsPlain.size(); S.ldsPerWave = ldsPerWave;
+  S.unitsEx = ( int ) unitsEx.size(); S.ldsPerWaveEx = ldsPerWaveEx;
+  S.unitsBlend = ( int ) unitsBlend.size(); S.ldsPerWaveBlend = ldsPerWaveBlend;
+  S.key.swap( key );
   return VVHIP_OK;
 }
 
-int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host, int n, int bit_depth,
-                    int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
+int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host,
+                    const vvhip_pred_blend* blend_host, int n, int bit_depth, int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
 {
   if( !ctx ) return VVHIP_E_ARG;
   if( !planes_host || n_planes < 1 || n_planes > 16 || n < 0 || n > ( 1 << 24 ) || bit_depth < 8 || bit_depth > 12 || pred_stride < 0 || ( n && ( !items_host || !d_pred ) ) || ( d_resi && !d_org ) )
@@ -693,26 +829,29 @@ int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_pla
 
   // ---- a list that is run again (same items, same plane table) is launched at once: no sort, no upload, no allocation, no wait — such a call can be recorded in a launch graph
   //      (the extensions are part of the list: the same items with other extensions are another schedule)
-  const size_t bKeyItems = sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ) + ( size_t ) n * sizeof( vvhip_pred_item );
-  std::vector<unsigned char> key( bKeyItems + ( ext_host ? ( size_t ) n * sizeof( vvhip_pred_ext ) : 0 ) );
-  if( ext_host ) memcpy( key.data() + bKeyItems, ext_host, ( size_t ) n * sizeof( vvhip_pred_ext ) );
+  //      A list with a blend array keeps a schedule of its own (and its array is part of its key).
+  vvhip_ctx::PredSched& S = ctx->predSched[blend_host ? 1 : 0];
+  const size_t bKeyItems = sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ) + ( size_t ) n * sizeof( vvhip_pred_item ), bKeyExt = ext_host ? ( size_t ) n * sizeof( vvhip_pred_ext ) : 0;
+  std::vector<unsigned char> key( bKeyItems + bKeyExt + ( blend_host ? 1 + ( size_t ) n * sizeof( vvhip_pred_blend ) : 0 ) );
+  if( ext_host ) memcpy( key.data() + bKeyItems, ext_host, bKeyExt );
+  if( blend_host ) { key[bKeyItems + bKeyExt] = ext_host ? 1 : 0; memcpy( key.data() + bKeyItems + bKeyExt + 1, blend_host, ( size_t ) n * sizeof( vvhip_pred_blend ) ); }
   memcpy( key.data(), &n_planes, sizeof( int ) );
   memcpy( key.data() + sizeof( int ), planes_host, ( size_t ) n_planes * sizeof( vvhip_me_plane ) );
   memcpy( key.data() + sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ), items_host, ( size_t ) n * sizeof( vvhip_pred_item ) );
-  if( key != ctx->predKey )
+  if( key != S.key )
   {
-    const int rc = predBuildSchedule( ctx, planes_host, n_planes, items_host, ext_host, n, key );
+    const int rc = predBuildSchedule( ctx, S, planes_host, n_planes, items_host, ext_host, blend_host, n, key );
     if( rc ) return rc;
   }
-  else if( ctx->predStream != ctx->stream )      // same schedule, other stream: order it behind the upload
+  else if( S.stream != ctx->stream )      // same schedule, other stream: order it behind the upload
   {
-    if( ctx->predEventRecorded ) VVHIP_CHECK_HIP( ctx, hipStreamWaitEvent( ctx->stream, ctx->predEvent, 0 ) );
-    ctx->predStream = ctx->stream;
+    if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipStreamWaitEvent( ctx->stream, S.event, 0 ) );
+    S.stream = ctx->stream;
   }
-  const size_t bItems = ctx->predOffSubs, bSubs = ctx->predOffUnits - ctx->predOffSubs;
-  const int ldsPerWave = ctx->predLdsPerWave, nUnits = ctx->predUnits;
+  const size_t bItems = S.offSubs, bSubs = S.offUnits - S.offSubs;
+  const int ldsPerWave = S.ldsPerWave, nUnits = S.units;
   PredArgs a;
-  const char* base = static_cast<const char*>( ctx->d_predSched );
+  const char* base = static_cast<const char*>( S.d_sched );
   a.items = reinterpret_cast<const PredDev*>( base ); a.subs = reinterpret_cast<const PredSub*>( base + bItems ); a.units = reinterpret_cast<const PredUnit*>( base + bItems + bSubs );
   a.nUnits = nUnits; a.bitDepth = bit_depth; a.ldsPerWave = ldsPerWave;
   a.pred = d_pred; a.predStride = pred_stride; a.org = d_resi ? d_org : nullptr; a.orgStride = org_stride; a.resi = d_resi;
@@ -721,19 +860,26 @@ int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_pla
     hipLaunchKernelGGL( predListKernel, dim3( ( unsigned ) ( nUnits / 4 ) ), dim3( 256 ), ( size_t ) ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a );
     VVHIP_LAUNCH_CHECK( ctx );
   }
-  if( ctx->predUnitsEx )
+  if( S.unitsEx )
   {
-    a.units += nUnits; a.nUnits = ctx->predUnitsEx; a.ldsPerWave = ctx->predLdsPerWaveEx;
+    a.units += nUnits; a.nUnits = S.unitsEx; a.ldsPerWave = S.ldsPerWaveEx;
     hipLaunchKernelGGL( predListExKernel, dim3( ( unsigned ) ( a.nUnits / 4 ) ), dim3( 256 ), ( size_t ) a.ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a );
+    VVHIP_LAUNCH_CHECK( ctx );
+  }
+  if( S.unitsBlend )
+  {
+    a.units = reinterpret_cast<const PredUnit*>( base + bItems + bSubs ) + nUnits + S.unitsEx; a.nUnits = S.unitsBlend; a.ldsPerWave = S.ldsPerWaveBlend;
+    hipLaunchKernelGGL( predListBlendKernel, dim3( ( unsigned ) ( a.nUnits / 4 ) ), dim3( 256 ), ( size_t ) a.ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a,
+                        reinterpret_cast<const PredBlendDev*>( base + S.offBlend ) );
     VVHIP_LAUNCH_CHECK( ctx );
   }
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if( hipStreamIsCapturing( ctx->stream, &cap ) != hipSuccess ) cap = hipStreamCaptureStatusNone;
   if( cap == hipStreamCaptureStatusNone )      // (a launch recorded into a graph runs later: the graph's owner keeps the list unchanged while the graph is in use)
   {
-    if( !ctx->predEvent ) VVHIP_CHECK_HIP( ctx, hipEventCreateWithFlags( &ctx->predEvent, hipEventDisableTiming ) );
-    VVHIP_CHECK_HIP( ctx, hipEventRecord( ctx->predEvent, ctx->stream ) );
-    ctx->predEventRecorded = true;
+    if( !S.event ) VVHIP_CHECK_HIP( ctx, hipEventCreateWithFlags( &S.event, hipEventDisableTiming ) );
+    VVHIP_CHECK_HIP( ctx, hipEventRecord( S.event, ctx->stream ) );
+    S.eventRecorded = true;
   }
   return VVHIP_OK;
 }
@@ -745,13 +891,29 @@ extern "C" {
 int vvhip_pred_inter_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, int n, int bit_depth,
                             int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
 {
-  return predInterBatch( ctx, planes_host, n_planes, items_host, nullptr, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
+  return predInterBatch( ctx, planes_host, n_planes, items_host, nullptr, nullptr, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
 }
 
 int vvhip_pred_inter_batch_ex( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host, int n, int bit_depth,
                                int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
 {
-  return predInterBatch( ctx, planes_host, n_planes, items_host, ext_host, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
+  return predInterBatch( ctx, planes_host, n_planes, items_host, ext_host, nullptr, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
+}
+
+int vvhip_pred_inter_batch_blend( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host,
+                                  const vvhip_pred_blend* blend_host, int n, int bit_depth, int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
+{
+  return predInterBatch( ctx, planes_host, n_planes, items_host, ext_host, blend_host, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
+}
+
+int vvhip_get_geo_weights_host( int split_dir, int log2_cu_w, int log2_cu_h, int chroma, int8_t* host_out )
+{
+  if( split_dir < 0 || split_dir > 63 || log2_cu_w < 3 || log2_cu_w > 6 || log2_cu_h < 3 || log2_cu_h > 6 || chroma < 0 || chroma > 1 || !host_out ) return VVHIP_E_ARG;
+  PredBlendDev g;
+  geoLine( split_dir, log2_cu_w, log2_cu_h, chroma, g );
+  const int w = ( 1 << log2_cu_w ) >> chroma, h = ( 1 << log2_cu_h ) >> chroma;
+  for( int y = 0; y < h; y++ ) for( int x = 0; x < w; x++ ) host_out[y * w + x] = ( int8_t ) vvhipBlendW0( g.a, g.b, g.c, g.lo, g.hi, x, y );
+  return VVHIP_OK;
 }
 
 int vvhip_interp_chroma_batch( vvhip_ctx* ctx, const int16_t* d_ref, int ref_stride, const vvhip_subpel_item* d_items, int n,

@@ -27,6 +27,8 @@ PRED_ITEM_DTYPE = np.dtype([("dst_off", "<i4"), ("org_off", "<i4"), ("ref_off", 
                             ("ref_plane", "i1", (2,)), ("chroma", "u1"), ("alt_hpel", "u1")])      # vvhip_pred_item (32 bytes)
 PRED_EXT_DTYPE = np.dtype([("flags", "u1"), ("pad_dx", "i1", (2,)), ("pad_dy", "i1", (2,)), ("rsv", "u1", (3,))])      # vvhip_pred_ext (8 bytes)
 PRED_EXT_BDOF, PRED_EXT_DMVR_PAD = 1, 2
+PRED_BLEND_DTYPE = np.dtype([("mode", "u1"), ("param", "u1"), ("rsv", "u1", (2,))])      # vvhip_pred_blend (4 bytes)
+PRED_BLEND_DEFAULT, PRED_BLEND_BCW, PRED_BLEND_GEO = 0, 1, 2      # param: - / bcw_idx 0..4 / geoSplitDir 0..63
 PRED_AFFINE_ITEM_DTYPE = np.dtype([("dst_off", "<i4"), ("org_off", "<i4"), ("ref_off", "<i4", (2,)), ("cpmv", "<i4", (2, 3, 2)), ("cu_x", "<i2"), ("cu_y", "<i2"), ("cu_w", "<i2"),
                                    ("cu_h", "<i2"), ("ref_plane", "i1", (2,)), ("chroma", "u1"), ("six_param", "u1"), ("prof", "u1"), ("rsv", "u1", (3,))])      # vvhip_pred_affine_item (80 bytes)
 
@@ -565,13 +567,24 @@ class HotPath:
     class _MePlane(C.Structure):          # vvhip_me_plane
         _fields_ = [("d_base", C.c_void_p), ("stride", C.c_int32), ("reserved", C.c_int32)]
 
-    def pred_inter_batch(self, planes, items, pred, pred_stride=0, bit_depth=10, org=None, resi=None, ext=None):
+    def pred_inter_batch(self, planes, items, pred, pred_stride=0, bit_depth=10, org=None, resi=None, ext=None, blend=None):
         """inter prediction of a list of prediction units in one launch: planes = the reference Planes the items' ref_plane indexes, items = PRED_ITEM_DTYPE records
         (HOST array: the library sorts it into size classes), pred = int16 tensor (compact blocks at dst_off, or a plane of row pitch pred_stride).
         org (a Plane) + resi (int16 tensor laid out like pred): also writes org - pred.
-        ext = PRED_EXT_DTYPE records parallel to items (BDOF, DMVR's padded reference): vvhip_pred_inter_batch_ex."""
+        ext = PRED_EXT_DTYPE records parallel to items (BDOF, DMVR's padded reference): vvhip_pred_inter_batch_ex.
+        blend = PRED_BLEND_DTYPE records parallel to items (BCW weights, GEO partitions): vvhip_pred_inter_batch_blend, with ext or without."""
         it = np.ascontiguousarray(items, PRED_ITEM_DTYPE)
         tab = (self._MePlane * max(1, len(planes)))(*[self._MePlane(p.buf_ptr.value, p.stride, 0) for p in planes])
+        if blend is not None:
+            bl = np.ascontiguousarray(blend, PRED_BLEND_DTYPE)
+            ex = np.ascontiguousarray(ext, PRED_EXT_DTYPE) if ext is not None else None
+            if bl.size != it.size or (ex is not None and ex.size != it.size):
+                raise ValueError("pred_inter_batch: %d blend records, %s extensions for %d items" % (bl.size, "no" if ex is None else ex.size, it.size))
+            self._ck(self.L.vvhip_pred_inter_batch_blend(self.ctx, C.cast(tab, C.c_void_p), len(planes), it.ctypes.data_as(C.c_void_p) if it.size else None,
+                                                         ex.ctypes.data_as(C.c_void_p) if ex is not None and ex.size else None,
+                                                         bl.ctypes.data_as(C.c_void_p) if bl.size else None, int(it.size), bit_depth, _ptr(pred), pred_stride,
+                                                         org.buf_ptr if org is not None else None, org.stride if org is not None else 0, _ptr(resi)))
+            return pred
         if ext is not None:
             ex = np.ascontiguousarray(ext, PRED_EXT_DTYPE)
             if ex.size != it.size:
@@ -583,6 +596,14 @@ class HotPath:
         self._ck(self.L.vvhip_pred_inter_batch(self.ctx, C.cast(tab, C.c_void_p), len(planes), it.ctypes.data_as(C.c_void_p) if it.size else None, int(it.size), bit_depth,
                                                _ptr(pred), pred_stride, org.buf_ptr if org is not None else None, org.stride if org is not None else 0, _ptr(resi)))
         return pred
+
+    def geo_weights(self, split_dir, cu_w, cu_h, chroma=0):
+        """the GEO weights w0 (0..8) of one component block of a cu_w x cu_h CU as the blend entry applies them (vvhip_get_geo_weights_host; host only) -> int8 [h, w]"""
+        w, h = cu_w >> chroma, cu_h >> chroma
+        out = np.zeros((h, w), np.int8)
+        if self.L.vvhip_get_geo_weights_host(int(split_dir), int(cu_w).bit_length() - 1, int(cu_h).bit_length() - 1, int(chroma), out.ctypes.data_as(C.c_void_p)) != 0:
+            raise ValueError("geo_weights: split_dir %d (0..63), CU %dx%d (8..64), chroma %d" % (split_dir, cu_w, cu_h, chroma))
+        return out
 
     def pred_affine_batch(self, planes, items, pred, pred_stride, bit_depth, pic_w, pic_h, ctu, org=None, resi=None):
         """inter prediction of a list of affine CUs from their control-point vectors in one launch (vvhip_pred_affine_batch): items = PRED_AFFINE_ITEM_DTYPE records, one

@@ -86,6 +86,7 @@ PROTOTYPES = {
     "vvhip_interp_chroma_batch": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "vvhip_pred_inter_batch": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, vp, i32, vp]),
     "vvhip_pred_inter_batch_ex": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, i32, vp, i32, vp]),
+    "vvhip_pred_inter_batch_blend": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp]),
     "vvhip_pred_affine_batch": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp]),
     "vvhip_subpel_dist_batch": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "vvhip_mctf_apply_plane": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, C.c_double, C.c_double, vp, i32]),
@@ -105,6 +106,7 @@ PROTOTYPES = {
     "vvhip_get_tr_matrix_host": (i32, [i32, i32, vp]),
     "vvhip_get_scan_order_host": (i32, [i32, i32, vp]),
     "vvhip_get_me_tap_tables_host": (i32, [i32, vp]),
+    "vvhip_get_geo_weights_host": (i32, [i32, i32, i32, i32, vp]),
     "vvhip_mctf_error_batch": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
     "vvhip_mctf_calc_var_batch": (i32, [vp, vp, i32, i32, i32, vp, i32, vp]),
     "vvhip_mctf_subsample": (i32, [vp, vp, i32, i32, i32, vp, i32, i32]),
