@@ -710,7 +710,8 @@ VVHIP_API int vvhip_alf_stats_plane( vvhip_ctx* ctx, const int16_t* d_org, int o
                                      int filter_length, const uint8_t* d_cls /* NULL: chroma */, int vb_ctu_height, int vb_pos, const float* d_init /* may be NULL */, float* d_out );
 
 /* The same with statistics units larger than a CTU (alfUnitSize > CTU size, EncAdaptiveLoopFilter::getStatisticsASU :1568-1590): one record set per unit of
- * unit_size x unit_size samples (<= 128), the float chains run through the unit's CTUs (ctu_size, raster order) and the blocks inside each CTU.          */
+ * unit_size x unit_size samples (<= 128), the float chains run through the unit's CTUs (ctu_size >= 8 dividing unit_size, raster order) and the blocks inside
+ * each CTU.                                                                                                                                                */
 VVHIP_API int vvhip_alf_stats_plane_units( vvhip_ctx* ctx, const int16_t* d_org, int org_stride, const int16_t* d_rec, int rec_stride, int width, int height, int unit_size,
                                            int ctu_size, int filter_length, const uint8_t* d_cls, int vb_ctu_height, int vb_pos, const float* d_init, float* d_out );
 
@@ -729,7 +730,8 @@ VVHIP_API int vvhip_ccalf_stats_plane( vvhip_ctx* ctx, const int16_t* d_org_c, i
  * d_coeff / d_clip: [num_sets][numClasses][13] int16 — the reference's m_coeffApsLuma / m_fixedFilterSetCoeffDec / m_chromaCoeffFinal rows and the matching clipping values;
  * d_clip == NULL selects the linear table entries (m_filter*Blk[0]: the x86 row ignores the clipping values there).  d_ctu_set[ctu]: filter set (luma: alfCtuFilterIndex;
  * chroma: m_ctuAlternative) of the CTU, < 0 = m_ctuEnableFlag off (the CTU's samples in d_dst stay untouched).  d_src carries a replicated border of >= 4 samples and must not
- * overlap d_dst; any strides (in samples) and alignment.  vb_ctu_height / vb_pos as in vvhip_alf_classify (chroma: m_alfVBChmaCTUHeight / m_alfVBChmaPos).                       */
+ * overlap d_dst; any strides (in samples) and alignment.  vb_ctu_height / vb_pos as in vvhip_alf_classify (chroma: m_alfVBChmaCTUHeight / m_alfVBChmaPos).
+ * The sums are int32 like the reference's scalar row at every bit depth; its x86 row saturates sum >> 7 at 16 bits, which 12-bit samples reach once sum |c_k| exceeds 512.       */
 VVHIP_API int vvhip_alf_filter_plane( vvhip_ctx* ctx, const int16_t* d_src, ptrdiff_t src_stride, int16_t* d_dst, ptrdiff_t dst_stride, int width, int height, int ctu_size, int bit_depth,
                                       int filter_length, const uint8_t* d_cls, const int16_t* d_coeff, const int16_t* d_clip /* NULL: linear */, const int16_t* d_ctu_set,
                                       int vb_ctu_height, int vb_pos );

@@ -305,7 +305,9 @@ alfOrderedAddKernel( AlfStatArgs A )
   // traversal: a statistics unit may consist of several CTUs (alfUnitSize > CTU size): CTU by CTU in raster order, blocks in raster order inside
   // a CTU (getStatisticsASU, :1568-1590).  Step s = (CTU row sy, CTU column sx, block row br inside the CTU); subBlk = CTU size in blocks.
   const int subBlk = A.subBlk, nSubX = ( nb + subBlk - 1 ) / subBlk, nSubY = ( rows + subBlk - 1 ) / subBlk, steps = nSubY * nSubX * subBlk;
-  __shared__ uint16_t sStep[4 * ALF_MAXB + 8];               // step -> unit block row | first block << 8 (computed once: no divisions in the ordered loop)
+  // step -> unit block row | first block << 8 (computed once: no divisions in the ordered loop).  The argument check admits CTUs of 8 inside units of 128:
+  // steps = nSubY * nSubX * subBlk <= ALF_MAXB * ALF_MAXB / subBlk <= ALF_MAXB * ALF_MAXB / 2, + the 8 entries the fetches look ahead
+  __shared__ uint16_t sStep[ALF_MAXB * ALF_MAXB / 2 + 8];
   for( int st = tid; st < steps + 8; st += 128 )
   {
     const int sy = st / ( nSubX * subBlk ), rem = st - sy * nSubX * subBlk, sx = rem / subBlk;
