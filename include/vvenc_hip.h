@@ -444,8 +444,9 @@ VVHIP_API int  vvhip_me_plan_info( const vvhip_me_plan* plan, int* waves_int, in
  * refinement is zero and for every PU BDOF does not apply to.
  * Affine CUs with PROF have an entry of their own that takes the control-point vectors: vvhip_pred_affine_batch below.
  * BCW's block weights and GEO's per-sample blending of two hypotheses are per-item blend records: vvhip_pred_inter_batch_blend below.
- * NOT done here (the caller's job, as before): explicit weighted prediction (slice-level weight tables); CIIP (needs intra prediction); IBC; reference picture resampling;
- * the chroma phases of 4:2:2 and 4:4:4.
+ * CIIP's planar intra part and its weighting are per-item CIIP records: vvhip_pred_inter_batch_ciip below.
+ * NOT done here (the caller's job, as before): explicit weighted prediction (slice-level weight tables); IBC; CIIP in a picture with LMCS active (the forward luma mapping
+ * before the weighting); reference picture resampling; the chroma phases of 4:2:2 and 4:4:4.
  * ====================================================================================================================== */
 typedef struct
 {
@@ -509,7 +510,7 @@ VVHIP_API int vvhip_pred_inter_batch_ex( vvhip_ctx* ctx, const vvhip_me_plane* p
  * InterPrediction.cpp:478, :975).  Everything vvhip_pred_inter_batch promises holds: order independence, both output layouts, the residual, the schedule cache — the blend
  * array is part of the list's key, and a list with a blend array keeps a schedule of its own: alternating with vvhip_pred_inter_batch[_ex] and vvhip_pred_affine_batch on one
  * context evicts none of the three.
- * Still the caller's: explicit weighted prediction, CIIP, IBC.                                                                                                          */
+ * CIIP has a record of its own: vvhip_pred_inter_batch_ciip below.  Still the caller's: explicit weighted prediction, IBC.                                             */
 #define VVHIP_PRED_BLEND_DEFAULT 0   /* exactly what the item does without a blend record     */
 #define VVHIP_PRED_BLEND_BCW     1   /* param = bcw_idx 0..4                                  */
 #define VVHIP_PRED_BLEND_GEO     2   /* param = geoSplitDir 0..63                             */
@@ -518,6 +519,34 @@ VVHIP_API int vvhip_pred_inter_batch_blend( vvhip_ctx* ctx, const vvhip_me_plane
                                             const vvhip_pred_ext* ext_host /* may be NULL */, const vvhip_pred_blend* blend_host /* may be NULL */, int n, int bit_depth,
                                             int16_t* d_pred, int pred_stride,
                                             const int16_t* d_org /* may be NULL */, int org_stride, int16_t* d_resi /* may be NULL */ );
+/* The same entry with a per-item CIIP record (ciip_host: a HOST array parallel to items_host; NULL = exactly vvhip_pred_inter_batch_blend) and the intra reference samples
+ * of the CIIP items (d_intra_ref: a DEVICE array, like the planes — its contents may change between runs of one list; neither they nor its address belong to the list's key).
+ *   VVHIP_PRED_CIIP_OFF : the item is what it is without a CIIP record.
+ *   VVHIP_PRED_CIIP_ON  : the item is a WHOLE component block of a CIIP CU (EncCu.cpp:1926, :2213-2219): luma w, h in 4..64 with w * h >= 64; a 4:2:0 chroma block 4..32
+ *               wide and 2..32 high with w * h >= 16.  Its inter part is the item's FINAL clipped sample — one list, the default average, or BCW through its blend record
+ *               (InterPrediction.cpp:973) — and the result is weightCiipCore (CommonLib/Buffer.cpp:60-81): ( wI * intra + ( 4 - wI ) * inter + 2 ) >> 2, wI = num_intra + 1,
+ *               not clipped.  num_intra 0..2 is getNumIntraCiip (IntraPrediction.h:176-188), computed by the caller.
+ *   intra     : IntraPrediction::predIntraAng with PLANAR_IDX (CommonLib/IntraPrediction.cpp:353-383).  d_intra_ref + ref_off holds top[0 .. w + 2] followed by
+ *               left[0 .. h + 2] — w + h + 6 samples in [0, 2^bit_depth), top[0] == left[0] the corner: the UNFILTERED samples of the two rows xFillReferenceSamples (:755)
+ *               leaves, neighbour availability and substitution done by the caller.  Nothing outside them is read.  Luma lines are smoothed with
+ *               ( u[i-1] + 2 u[i] + u[i+1] + 2 ) >> 2 (xFilterReferenceSamples :994-1030; refFilterFlag :473-476 holds for every CIIP luma block), chroma lines are not
+ *               (:461-468); then xPredIntraPlanar_Core (:79-135) and, where min( w, h ) >= 4 (:426), the PDPC of IntraPredSampleFilter_Core (:137-157) on the same line.
+ *               Blocks larger than a tile are cut as always; planar and PDPC are evaluated in block coordinates.
+ * Argument errors (VVHIP_E_ARG with a message naming this entry, nothing launched): unknown mode; num_intra > 2; non-zero rsv; a negative ref_off; a size outside the sets
+ * above; CIIP on a GEO item; CIIP on an item whose extension record carries VVHIP_PRED_EXT_BDOF or VVHIP_PRED_EXT_DMVR_PAD (InterPrediction.cpp:468, UnitTools.cpp:1309);
+ * d_intra_ref == NULL while any record is ON.  Everything vvhip_pred_inter_batch promises holds: order independence, both output layouts, the residual (taken from the CIIP
+ * result), the schedule cache — the CIIP array is part of the list's key, and a list with a CIIP array keeps a schedule of its own: alternating with
+ * vvhip_pred_inter_batch[_ex], vvhip_pred_inter_batch_blend and vvhip_pred_affine_batch on one context evicts none of them.
+ * Still the caller's: explicit weighted prediction, IBC, and CIIP in a picture with LMCS active (the forward luma mapping of the inter part before the weighting); of CIIP
+ * itself the CU-level conditions, the reference line and num_intra.                                                                                                      */
+#define VVHIP_PRED_CIIP_OFF 0   /* exactly what the item does without a CIIP record      */
+#define VVHIP_PRED_CIIP_ON  1   /* ref_off, num_intra as above                           */
+typedef struct { int32_t ref_off; uint8_t mode, num_intra, rsv[2]; } vvhip_pred_ciip;   /* 8 bytes, rsv zero */
+VVHIP_API int vvhip_pred_inter_batch_ciip( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host,
+                                           const vvhip_pred_ext* ext_host /* may be NULL */, const vvhip_pred_blend* blend_host /* may be NULL */,
+                                           const vvhip_pred_ciip* ciip_host /* may be NULL */, const int16_t* d_intra_ref /* may be NULL without an ON record */,
+                                           int n, int bit_depth, int16_t* d_pred, int pred_stride,
+                                           const int16_t* d_org /* may be NULL */, int org_stride, int16_t* d_resi /* may be NULL */ );
 /* Inter prediction of a LIST of AFFINE CUs from their control-point vectors: what InterPredInterpolation::xPredAffineBlk (CommonLib/InterPrediction.cpp:1497-1839) + the
  * default weighted average produce for one component block of one affine CU, PROF included, bit-exact.  One item is one component block; the CU record is all that
  * crosses to the device — the sub-block vectors, fractions and PROF's dMv table are derived in the kernel.

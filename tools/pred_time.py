@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/pred_time.py — what the prediction-list entry (vvhip_pred_inter_batch, vvenc_amd/csrc/pred.hip) costs on a 1920x1080 picture.
 
-  python tools/pred_time.py [--rounds 9] [--reps 40] [--other-lib PATH] [--json PATH] [--quick]
+  python tools/pred_time.py [--rounds 9] [--reps 40] [--other-lib PATH] [--json PATH] [--quick] [--ciip-only]
 
 A. the path it generalises: a picture's worth of luma 16x16 uni-prediction blocks (120 x 67 = 8040, seeded vectors within +-8 samples, all 256 phases) through
    vvhip_interp_luma_batch and through vvhip_pred_inter_batch — and, with --other-lib, through vvhip_interp_luma_batch of ANOTHER build of the library (the parent commit's)
@@ -18,6 +18,11 @@ C. the affine mix: seeded affine CUs AFFINE_HIST (sizes 16..64, half bi-predicte
 D. the blend mix: seeded two-hypothesis CUs BLEND_HIST (the GEO size range 8..64, 1080p positions, luma + Cb + Cr), half of them BCW (index 0, 1, 3 or 4) and half GEO
    (any split direction), through vvhip_pred_inter_batch_blend — and the same items as plain bi-predicted items (blend = NULL: the cost floor of these blocks) through
    a second context, in the same rounds.  Reported: both times, their ratio, and how many samples the blend records change.
+E. the CIIP mix: seeded CIIP CUs CIIP_HIST (the CIIP size range, 1080p positions, luma + Cb + Cr — the 2-wide chroma blocks of 4-wide CUs carry no CIIP, as in the
+   reference), half of them bi-predicted, a third per num_intra value, each block's reference line taken from the row above and the column left of it in the list-0
+   pictures, through vvhip_pred_inter_batch_ciip — and the same items with ciip = NULL (what these blocks cost without the intra part and the weighting: the cost
+   floor) through a second context, in the same rounds.  Reported: both times, their ratio, and the share of samples the CIIP records change.  --ciip-only: this
+   section alone.
 Every variant is recorded into a launch graph once and timed as `reps` graph launches between two host clock readings that end in a device synchronise, `rounds` times, the
 variants alternating inside a round; medians, minima and the spread ( max - min ) / median are printed.  --quick: one round of few launches (for a profiler run)."""
 import argparse
@@ -42,6 +47,8 @@ AFFINE_HIST = {(64, 64): 60, (32, 32): 200, (64, 32): 40, (32, 64): 40, (32, 16)
 AFFINE_CTU, AFFINE_D = 128, 32
 # two-hypothesis CUs with a blend record of one picture: (width, height) -> count
 BLEND_HIST = {(64, 64): 30, (32, 32): 90, (64, 32): 20, (32, 64): 20, (32, 16): 50, (16, 32): 50, (16, 16): 160, (16, 8): 40, (8, 16): 40, (8, 8): 100}
+# CIIP CUs of one picture: (width, height) -> count
+CIIP_HIST = {(64, 64): 30, (32, 32): 90, (64, 32): 20, (32, 64): 20, (32, 16): 50, (16, 32): 50, (16, 16): 160, (16, 8): 40, (8, 16): 40, (8, 8): 100, (16, 4): 20, (4, 16): 20}
 
 
 class OtherBuild:
@@ -187,6 +194,91 @@ def blend_items(rng, luma_stride, chroma_stride):
     return np.concatenate(recs)[order], np.concatenate(bl)[order], at
 
 
+def ciip_items(rng, luma_stride, chroma_stride, pics):
+    """luma + Cb + Cr items of every CU of CIIP_HIST; planes as b_picture_items; pics: the host pictures (Y, Cb, Cr) the reference lines are cut from.
+    -> (items, CIIP records, reference lines, samples)"""
+    from vvenc_amd.hotpath import PRED_CIIP_DTYPE, PRED_CIIP_ON, PRED_ITEM_DTYPE
+    padded = [np.pad(p, ((1, 2), (1, 2)), mode="edge") for p in pics]          # a block at the picture's edge takes the replicated neighbour
+    recs, ci, lines, at, lat, k = [], [], [], 0, 0, 0
+    for (w, h), count in CIIP_HIST.items():
+        for _ in range(count):
+            px, py = int(rng.integers(0, (W - w) // w + 1)) * w, int(rng.integers(0, (H - h) // h + 1)) * h
+            bi, first = bool(rng.integers(0, 2)), int(rng.integers(0, 2))
+            mv = [(int(rng.integers(-128, 129)), int(rng.integers(-128, 129))) for _ in range(2)]
+            for comp in range(3):
+                cs = 1 if comp else 0
+                it, c = np.zeros(1, PRED_ITEM_DTYPE), np.zeros(1, PRED_CIIP_DTYPE)
+                cw, chh, cx, cy = w >> cs, h >> cs, px >> cs, py >> cs
+                it["width"], it["height"], it["chroma"], it["dst_off"] = cw, chh, cs, at
+                sh, stride = 4 + cs, chroma_stride if cs else luma_stride
+                for l in (0, 1):
+                    if not bi and l != first:
+                        it["ref_plane"][0, l] = -1
+                        continue
+                    it["ref_plane"][0, l] = 2 * comp + l
+                    it["ref_off"][0, l] = (cy + (mv[l][1] >> sh)) * stride + cx + (mv[l][0] >> sh)
+                    it["frac"][0, l] = (mv[l][0] & ((1 << sh) - 1), mv[l][1] & ((1 << sh) - 1))
+                if cw >= 4:
+                    P = padded[comp]
+                    line = np.concatenate([P[cy, cx:cx + cw + 3], P[cy:cy + chh + 3, cx]])
+                    c["mode"], c["num_intra"], c["ref_off"] = PRED_CIIP_ON, k % 3, lat
+                    lines.append(line); lat += line.size
+                at += cw * chh
+                recs.append(it); ci.append(c)
+            k += 1
+    order = rng.permutation(len(recs))
+    return np.concatenate(recs)[order], np.concatenate(ci)[order], np.concatenate(lines).astype(np.int16), at
+
+
+def ciip_section(table, pics, a):
+    """section E -> its result record"""
+    import torch
+    from vvenc_amd.hotpath import HotPath
+    crng = np.random.default_rng(SEED + 3)
+    citems, cciip, clines, ctotal = ciip_items(crng, table[0].stride, table[2].stride, pics)
+    hpc, hpn = HotPath(), HotPath()
+    d_lines = torch.from_numpy(clines).to(hpc.device)
+    couts = [torch.zeros(ctotal, dtype=torch.int16, device=hpc.device) for _ in range(2)]
+    cfns = {"ciip_batch": (hpc, lambda: hpc.pred_inter_batch(table, citems, couts[0], 0, 10, ciip=cciip, intra_ref=d_lines)),
+            "same_items_no_ciip": (hpn, lambda: hpn.pred_inter_batch(table, citems, couts[1], 0, 10))}
+    cgraphs, cfirst = {}, {}
+    for name, (h, fn) in cfns.items():
+        h.use_own_stream()
+        t0 = time.perf_counter(); fn(); cfirst[name] = time.perf_counter() - t0
+        h.sync()
+        cgraphs[name] = h.graph_capture(fn)
+
+    def run_ciip(name, reps):
+        h = cfns[name][0]
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            h.graph_launch(cgraphs[name])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps
+    cnames = list(cfns)
+    ctimes = {k: [] for k in cnames}
+    for k in cnames:
+        run_ciip(k, 5)
+    for r in range(a.rounds):
+        for k in (cnames if r % 2 == 0 else cnames[::-1]):
+            ctimes[k].append(run_ciip(k, a.reps))
+    cst = {k: stats(v) for k, v in ctimes.items()}
+    on = cciip["mode"] == 1
+    changed = int((couts[0] != couts[1]).sum().item())
+    return {"cus": int(sum(CIIP_HIST.values())), "items": int(len(citems)), "ciip_items": int(on.sum()), "bi_items": int(((citems["ref_plane"][:, 0] >= 0) & (citems["ref_plane"][:, 1] >= 0)).sum()),
+            "samples": int(ctotal), "line_samples": int(clines.size), **cst, "ratio_to_no_ciip": round(cst["ciip_batch"]["median_us"] / cst["same_items_no_ciip"]["median_us"], 3),
+            "changed_samples": changed, "changed_share": round(changed / ctotal, 4), "host_first_call_us": {k: round(v * 1e6, 1) for k, v in cfirst.items()}}
+
+
+def finish(res, a):
+    for k, v in res.items():
+        print(k, json.dumps(v) if isinstance(v, dict) else v)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def stats(ts):
     ts = sorted(ts)
     med = ts[len(ts) // 2]
@@ -200,6 +292,7 @@ def main():
     ap.add_argument("--other-lib", default=None, help="another build of libvvenc_hip.so: its vvhip_interp_luma_batch is timed in the same rounds")
     ap.add_argument("--json", default=None)
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--ciip-only", action="store_true", help="section E alone")
     a = ap.parse_args()
     if a.quick:
         a.rounds, a.reps = 1, 5
@@ -218,6 +311,10 @@ def main():
     org_np[H:, :W // 2], org_np[H:, W // 2:] = chroma_of(y1, 0), chroma_of(y1, 1)
     org = hp.plane(org_np, 0)
     res = {"picture": [W, H], "rounds": a.rounds, "reps": a.reps}
+    pics = [y0, chroma_of(y0, 0), chroma_of(y0, 1)]
+    if a.ciip_only:
+        res["ciip_mix"] = ciip_section([luma[0], luma[1], chroma[0], chroma[1], chroma[2], chroma[3]], pics, a)
+        return finish(res, a)
 
     # ---- A: luma 16x16 uni-prediction, old entry / new entry / the other build's old entry
     sp, it = luma16_items(rng, luma[0].stride)
@@ -405,12 +502,9 @@ def main():
     res["blend_mix"] = {"cus": int(sum(BLEND_HIST.values())), "items": int(len(bitems)), "bcw_items": int((bblend["mode"] == 1).sum()), "geo_items": int((bblend["mode"] == 2).sum()),
                         "samples": int(btotal), **bst, "ratio_to_plain": round(bst["blend_batch"]["median_us"] / bst["same_items_plain_bi"]["median_us"], 3),
                         "changed_samples": int((bouts[0] != bouts[1]).sum().item()), "host_first_call_us": {k: round(v * 1e6, 1) for k, v in bfirst.items()}}
-    for k, v in res.items():
-        print(k, json.dumps(v) if isinstance(v, dict) else v)
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
-    print(json.dumps(res))
+    # ---- E: the CIIP mix through vvhip_pred_inter_batch_ciip, and the same items without their CIIP records
+    res["ciip_mix"] = ciip_section(table, pics, a)
+    finish(res, a)
 
 
 if __name__ == "__main__":

@@ -41,21 +41,22 @@ struct vvhip_ctx
   hipEvent_t   tuGenEvent  = nullptr;      // recorded behind every launch that reads the table: a caller that switches streams orders the new stream behind it
   bool         tuGenEventRecorded = false;
   // device copy of the schedule of vvhip_pred_inter_batch (pred.hip), the caller's list it was derived from (items + plane table: a list that is run again is neither sorted
-  // nor uploaded again) and the host copy the asynchronous upload reads.  [0]: vvhip_pred_inter_batch[_ex]; [1]: vvhip_pred_inter_batch_blend called with a blend array —
-  // a schedule, key, host copy and event of its own, so that alternating the entries on one context evicts neither
+  // nor uploaded again) and the host copy the asynchronous upload reads.  [0]: vvhip_pred_inter_batch[_ex]; [1]: vvhip_pred_inter_batch_blend called with a blend array;
+  // [2]: vvhip_pred_inter_batch_ciip called with a CIIP array — each a schedule, key, host copy and event of its own, so that alternating the entries on one context evicts none
   struct PredSched
   {
     void*        d_sched   = nullptr;
     size_t       bytes     = 0;
     std::vector<unsigned char> key, blob;
-    size_t       offSubs   = 0, offUnits = 0, offBlend = 0;
+    size_t       offSubs   = 0, offUnits = 0, offBlend = 0, offCiip = 0;
     int          units     = 0, ldsPerWave = 0;
     int          unitsEx   = 0, ldsPerWaveEx = 0;          // the units of items with an extension (BDOF, DMVR's padded reference): behind the plain units, a kernel of their own
     int          unitsBlend = 0, ldsPerWaveBlend = 0;      // the units of BCW / GEO items: behind those, a kernel of their own; their records sit at offBlend
+    int          unitsCiip = 0, ldsPerWaveCiip = 0;        // the units of CIIP items: behind those, a kernel of their own; their records sit at offCiip
     hipStream_t  stream    = nullptr;      // the stream the schedule was uploaded on; compared only, never used as a handle
     hipEvent_t   event     = nullptr;      // recorded behind every launch that reads the schedule
     bool         eventRecorded = false;
-  } predSched[2];
+  } predSched[3];
   // the same for vvhip_pred_affine_batch (predaffine.hip): a schedule, key, host copy and event of its own — alternating the two entries on one context evicts neither
   void*        d_affSched = nullptr;
   size_t       affBytes   = 0;

@@ -871,9 +871,9 @@ bool DMVROps::refineCu( const Pel* ref0, int stride0, int fx0, int fy0, const Pe
 
 // ------------------------------------------------------------------------------------------------ InterPredOps
 bool InterPredOps::predictList( const Pel* const* refPlanes, int numPlanes, const vvhip_pred_item* items, int n, int bitDepth, Pel* pred, size_t predElems, const Pel* org, Pel* resi,
-                                const vvhip_pred_ext* ext, const vvhip_pred_blend* blend )
+                                const vvhip_pred_ext* ext, const vvhip_pred_blend* blend, const vvhip_pred_ciip* ciip, const Pel* intraRef, size_t intraRefElems )
 {
-  if( numPlanes < 1 || numPlanes > 16 || n < 0 || !pred || ( resi && !org ) ) return false;
+  if( numPlanes < 1 || numPlanes > 16 || n < 0 || !pred || ( resi && !org ) || ( intraRefElems && !intraRef ) ) return false;
   Device& dev = Device::get();
   auto mirrorOf = [&dev]( const Pel* p ) { Device::Found f = dev.findReference( p ); return f ? f : dev.find( p ); };
   vvhip_me_plane table[16];
@@ -894,7 +894,17 @@ bool InterPredOps::predictList( const Pel* const* refPlanes, int numPlanes, cons
   const size_t bytes = ( predElems * sizeof( Pel ) + 255 ) & ~( size_t ) 255;
   int16_t* dPred = dev.staging( ( resi ? 2 : 1 ) * bytes + 256 );
   int16_t* dResi = resi ? dPred + bytes / sizeof( Pel ) : nullptr;
-  if( blend ) dev.check( vvhip_pred_inter_batch_blend( dev.ctx(), table, numPlanes, items, ext, blend, n, bitDepth, dPred, 0, dOrg, orgStride, dResi ), "vvhip_pred_inter_batch_blend" );
+  if( ciip )
+  {
+    int16_t* dLine = nullptr;      // the lines travel with the list: they are the neighbours' reconstruction of this moment
+    if( intraRefElems )
+    {
+      dLine = static_cast<int16_t*>( dev.stagingAux( intraRefElems * sizeof( Pel ) + 64 ) );
+      dev.check( vvhip_upload( dev.ctx(), dLine, intraRef, intraRefElems * sizeof( Pel ) ), "CIIP intra reference samples" );
+    }
+    dev.check( vvhip_pred_inter_batch_ciip( dev.ctx(), table, numPlanes, items, ext, blend, ciip, dLine, n, bitDepth, dPred, 0, dOrg, orgStride, dResi ), "vvhip_pred_inter_batch_ciip" );
+  }
+  else if( blend ) dev.check( vvhip_pred_inter_batch_blend( dev.ctx(), table, numPlanes, items, ext, blend, n, bitDepth, dPred, 0, dOrg, orgStride, dResi ), "vvhip_pred_inter_batch_blend" );
   else if( ext ) dev.check( vvhip_pred_inter_batch_ex( dev.ctx(), table, numPlanes, items, ext, n, bitDepth, dPred, 0, dOrg, orgStride, dResi ), "vvhip_pred_inter_batch_ex" );
   else dev.check( vvhip_pred_inter_batch( dev.ctx(), table, numPlanes, items, n, bitDepth, dPred, 0, dOrg, orgStride, dResi ), "vvhip_pred_inter_batch" );
   if( resi ) dev.check( vvhip_download_async( dev.ctx(), resi, dResi, predElems * sizeof( Pel ) ), "prediction list residual" );

@@ -244,9 +244,13 @@ struct InterPredOps
   // ext (may be nullptr): vvhip_pred_ext records parallel to items — BDOF on true bi-predicted luma blocks, DMVR's padded reference for refined sub-blocks
   // (vvhip_pred_inter_batch_ex).
   // blend (may be nullptr): vvhip_pred_blend records parallel to items — BCW's block weights and GEO's per-sample blending of two hypotheses; a GEO item is a whole
-  // component block of its CU (vvhip_pred_inter_batch_blend).  Explicit weighted prediction, CIIP and IBC stay with the caller.
+  // component block of its CU (vvhip_pred_inter_batch_blend).
+  // ciip (may be nullptr): vvhip_pred_ciip records parallel to items — the planar intra part and the weighting of CIIP CUs; an ON item is a whole component block of its
+  // CU and its ref_off points into intraRef, a HOST array of intraRefElems samples (per item top[0 .. w + 2], left[0 .. h + 2], unfiltered) that is uploaded with the list
+  // (vvhip_pred_inter_batch_ciip).  Explicit weighted prediction, IBC and CIIP in a picture with LMCS active stay with the caller.
   bool predictList( const Pel* const* refPlanes, int numPlanes, const vvhip_pred_item* items, int n, int bitDepth, Pel* pred, size_t predElems, const Pel* org = nullptr, Pel* resi = nullptr,
-                    const vvhip_pred_ext* ext = nullptr, const vvhip_pred_blend* blend = nullptr );
+                    const vvhip_pred_ext* ext = nullptr, const vvhip_pred_blend* blend = nullptr, const vvhip_pred_ciip* ciip = nullptr, const Pel* intraRef = nullptr,
+                    size_t intraRefElems = 0 );
   // The same for a list of affine CUs given by their control-point vectors (vvhip_pred_affine_batch: InterPredInterpolation::xPredAffineBlk, :1497-1839, PROF included):
   // items: vvhip_pred_affine_item records, one per component block, ref_off / org_off = the block's own position at the picture's line pitch; picWidth / picHeight / ctuSize
   // (luma) feed the picture clip.  Planes, outputs, residual and the return value as predictList.

@@ -26,8 +26,15 @@
 //   BCW   AreaBuf<Pel>::addWeightedAvg CommonLib/Buffer.cpp:509-546 (core :143-156), getBcwWeight Rom.cpp:1150-1163: w0 = 8 - { -2, 3, 4, 5, 10 }[bcw_idx] for the whole block
 //   GEO   InterpolationFilter::xWeightedGeoBlk CommonLib/InterpolationFilter.cpp:1005-1064, tables Rom.cpp:1304-1382: w0 per sample, a clamped line in ( x, y ) whose three
 //         integers the host derives from the split direction and the CU size (geoLine below; vvhipBlendW0 in common.h) — no weight table and no weight block on the device.
-// Still the caller's: the BDOF conditions on POC distances and CU flags, the CU-level conditions of BCW and GEO, explicit weighted prediction (slice-level weight tables),
-// CIIP (needs intra prediction), IBC.  Affine CUs with PROF have an entry of their own that takes the
+// Items with a CIIP record (vvhip_pred_inter_batch_ciip) run in predListCiipKernel, the same body with a step behind the combine: the final clipped inter sample (one list,
+//   the default average or BCW) is weighted with the PLANAR intra prediction of the block, ( wI * intra + ( 4 - wI ) * inter + 2 ) >> 2, wI = num_intra + 1, no clip
+//   CIIP  weightCiipCore CommonLib/Buffer.cpp:60-81; IntraPrediction::predIntraAng with PLANAR_IDX CommonLib/IntraPrediction.cpp:353-383: xFilterReferenceSamples :994-1030
+//         (luma only), xPredIntraPlanar_Core :79-135, IntraPredSampleFilter_Core :137-157 (PDPC, min( w, h ) >= 4).  The planar running sums are linear in x + 1 and
+//         y + 1, so a lane evaluates its own samples from the block's reference line in block coordinates; the line is read straight from the caller's device array
+//         (a lane needs its row's left sample, the two far corners and its own columns of the top row: a few cached loads, no LDS and no further wave barrier).
+// Still the caller's: the BDOF conditions on POC distances and CU flags, the CU-level conditions of BCW, GEO and CIIP (with the neighbour availability and substitution of
+// the intra reference line and getNumIntraCiip), explicit weighted prediction (slice-level weight tables), IBC, CIIP in a picture with LMCS active (the forward luma mapping
+// before the weighting).  Affine CUs with PROF have an entry of their own that takes the
 // control-point vectors (vvhip_pred_affine_batch, predaffine.hip: its own kernel and its own schedule cache; the 4x4 forms here are what it is checked against).
 #include <algorithm>
 #include <string.h>
@@ -59,8 +66,9 @@ struct __attribute__( ( aligned( 16 ) ) ) PredDev      // one prediction item wi
 };
 struct PredSub  { int32_t item; int16_t x0, y0; };      // one tile of an item
 struct PredBlendDev { int32_t a, b, c; int16_t lo, hi; };      // w0( x, y ) of a BCW / GEO item (vvhipBlendW0); parallel to the items, read by predListBlendKernel only
+struct PredCiipDev { int32_t refOff; int8_t w0; uint8_t wI, filt, pdpc; };      // a CIIP item: its line in the intra reference array, hypothesis 0's weight of the inter part (4: default average), num_intra + 1, luma smoothing, PDPC; read by predListCiipKernel only
 struct PredUnit { int32_t firstSub; int16_t nSub, tw, th; uint8_t kind, log2Lanes, log2SegsRow, pad[3]; };      // what one wave does (pad[0]: the extension flags of its class)
-static_assert( sizeof( PredDev ) == 48 && sizeof( PredSub ) == 8 && sizeof( PredUnit ) == 16 && sizeof( PredBlendDev ) == 16, "schedule records" );
+static_assert( sizeof( PredDev ) == 48 && sizeof( PredSub ) == 8 && sizeof( PredUnit ) == 16 && sizeof( PredBlendDev ) == 16 && sizeof( PredCiipDev ) == 8, "schedule records" );
 
 // kernel forms: samples per lane (a "segment": SEG horizontally adjacent samples) x taps per pass
 enum { KIND_L8 = 0, KIND_L4 = 1, KIND_C8 = 2, KIND_C4 = 3, KIND_C2 = 4 };
@@ -106,6 +114,9 @@ struct Lane
   int16_t* ext;
   // blend form only (predBody<.., FORM_BLEND>): the weight line of the item
   int ba, bb, bc, blo, bhi;
+  // CIIP form only (predBody<.., FORM_CIIP>): top[0 .. w + 2] then left[0 .. h + 2] of the block, hypothesis 0's weight, the intra weight, smoothing and PDPC on / off
+  const int16_t* line;
+  int cw0, cwI, cfilt, cpdpc;
 };
 
 #define PRED_WAVE_SYNC() { __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" ); __builtin_amdgcn_wave_barrier(); }
@@ -148,7 +159,11 @@ __device__ __forceinline__ int clampi( int v, int lo, int hi ) { return v < lo ?
 
 // FORM_PLAIN: the forms of vvhip_pred_inter_batch.  FORM_EX adds, per unit of the schedule, the DMVR clamp in the window staging and the BDOF form of the average.
 // FORM_BLEND replaces the average by the weighted one of BCW / GEO (both hypotheses present: the host checks it).
-enum { FORM_PLAIN = 0, FORM_EX = 1, FORM_BLEND = 2 };
+// FORM_CIIP takes uni- and bi-predicted items (the average with hypothesis 0's weight cw0: 4 is the default average) and weights the final sample with planar intra prediction.
+enum { FORM_PLAIN = 0, FORM_EX = 1, FORM_BLEND = 2, FORM_CIIP = 3 };
+
+// sample i ( >= 1 ) of one row of the intra reference line as planar and PDPC read it: smoothed for luma (xFilterReferenceSamples), as it is for chroma
+__device__ __forceinline__ int ciipRef( const int16_t* r, int i, int filt ) { const int c = r[i]; return filt ? ( ( int ) r[i - 1] + 2 * c + ( int ) r[i + 1] + 2 ) >> 2 : c; }
 template<int SEG, int NT, int FORM = FORM_PLAIN>
 __device__ __forceinline__ void predBody( const Lane& L, int tw, int th, int log2SegsRow, int lanes, int bitDepth )
 {
@@ -378,6 +393,12 @@ __device__ __forceinline__ void predBody( const Lane& L, int tw, int th, int log
       acc[j] = v < 0 ? 0 : ( v > maxv ? maxv : v );
     }
   }
+  else if( FORM == FORM_CIIP && L.mode == MODE_BI )      // the default average as w0 = 4 ( 4 ( a + b + offset ) >> ( shiftNum + 2 ) is the same number ), or BCW's
+  {
+    const int sn = hr + 3, off = ( 1 << ( sn - 1 ) ) + ( 8192 << 3 );
+#pragma unroll
+    for( int j = 0; j < SEG; j++ ) { const int v = ( L.cw0 * first[j] + ( 8 - L.cw0 ) * acc[j] + off ) >> sn; acc[j] = v < 0 ? 0 : ( v > maxv ? maxv : v ); }
+  }
   else if( L.mode == MODE_BI )      // addAvg: ClipPel( ( a + b + offset ) >> shiftNum ), shiftNum = headroom + 1, offset = ( 1 << headroom ) + 2 * IF_INTERNAL_OFFS (Buffer.cpp:129-141, :549-575)
   {
     const int sn = hr + 1, off = ( 1 << hr ) + 2 * 8192;
@@ -390,6 +411,28 @@ __device__ __forceinline__ void predBody( const Lane& L, int tw, int th, int log
     for( int j = 0; j < SEG; j++ ) acc[j] = first[j];
   }
   const int row = L.y0 + y, col = L.x0 + xs;
+  if( FORM == FORM_CIIP )
+  {
+    // planar at block coordinates ( col + j, row ): horPred = ( left << log2W ) + ( x + 1 ) * ( topRight - left ), vertPred = ( top << log2H ) + ( y + 1 ) * ( bottomLeft - top )
+    // (xPredIntraPlanar_Core's running sums, closed), then PDPC on the same line, then the weighting with the clipped inter sample.  12-bit samples: every term < 2^25.
+    const int16_t* top = L.line; const int16_t* left = L.line + L.w + 3;
+    const int l2w = 31 - __builtin_clz( ( unsigned ) L.w ), l2h = 31 - __builtin_clz( ( unsigned ) L.h ), scale = ( l2w + l2h - 2 ) >> 2;
+    const int lf = ciipRef( left, row + 1, L.cfilt ), tr = ciipRef( top, L.w + 1, L.cfilt ), bl = ciipRef( left, L.h + 1, L.cfilt );
+    const int wT = L.cpdpc ? 32 >> min( 31, ( 2 * row ) >> scale ) : 0;
+    int u[SEG + 2];
+#pragma unroll
+    for( int j = 0; j < SEG + 2; j++ ) u[j] = top[col + j];      // top[col .. col + SEG + 1], col + SEG <= w: inside top[0 .. w + 2]
+#pragma unroll
+    for( int j = 0; j < SEG; j++ )
+    {
+      const int t = L.cfilt ? ( u[j] + 2 * u[j + 1] + u[j + 2] + 2 ) >> 2 : u[j + 1];
+      const int hor = ( lf << l2w ) + ( col + j + 1 ) * ( tr - lf ), ver = ( t << l2h ) + ( row + 1 ) * ( bl - t );
+      int p = ( ( hor << l2h ) + ( ver << l2w ) + ( 1 << ( l2w + l2h ) ) ) >> ( 1 + l2w + l2h );
+      const int wL = L.cpdpc ? 32 >> min( 31, ( 2 * ( col + j ) ) >> scale ) : 0;
+      p += ( wL * ( lf - p ) + wT * ( t - p ) + 32 ) >> 6;
+      acc[j] = ( L.cwI * p + ( 4 - L.cwI ) * acc[j] + 2 ) >> 2;
+    }
+  }
   SegRow<SEG> o;
 #pragma unroll
   for( int j = 0; j < SEG; j++ ) o.v[j] = ( int16_t ) acc[j];
@@ -455,6 +498,17 @@ __device__ __forceinline__ void predDispatchBlend( int kind, const Lane& L, int 
   case KIND_C8: predBody<8, 4, FORM_BLEND>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
   case KIND_C4: predBody<4, 4, FORM_BLEND>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
   default:      predBody<2, 4, FORM_BLEND>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  }
+}
+
+__device__ __forceinline__ void predDispatchCiip( int kind, const Lane& L, int tw, int th, int log2SegsRow, int lanes, int bitDepth )
+{
+  switch( kind )      // wave-uniform (a CIIP block is at least 4 wide: no 2-sample form)
+  {
+  case KIND_L8: predBody<8, 8, FORM_CIIP>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_L4: predBody<4, 8, FORM_CIIP>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  case KIND_C8: predBody<8, 4, FORM_CIIP>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
+  default:      predBody<4, 4, FORM_CIIP>( L, tw, th, log2SegsRow, lanes, bitDepth ); break;
   }
 }
 
@@ -573,6 +627,39 @@ predListBlendKernel( PredArgs a, const PredBlendDev* __restrict__ blend )
   predDispatchBlend( u.kind, L, u.tw, u.th, u.log2SegsRow, lanes, a.bitDepth );
 }
 
+// the units of CIIP items (vvhip_pred_inter_batch_ciip): the item as it is otherwise — one list, the default average or BCW — then the weighting with planar intra prediction
+// from the item's line of the caller's reference-sample array.  A kernel of its own, as the other forms: they keep their registers.
+__global__ void __launch_bounds__( 256 )
+predListCiipKernel( PredArgs a, const PredCiipDev* __restrict__ ciip, const int16_t* __restrict__ intraRef )
+{
+  extern __shared__ __attribute__( ( aligned( 16 ) ) ) int16_t sPred[];
+  const int wave = __builtin_amdgcn_readfirstlane( ( int ) ( threadIdx.x >> 6 ) ), lane = threadIdx.x & 63;
+  const int ui = ( int ) blockIdx.x * 4 + wave;
+  if( ui >= a.nUnits ) return;
+  const PredUnit u = a.units[ui];
+  if( u.nSub == 0 ) return;
+  const int nt = u.kind <= KIND_L4 ? 8 : 4, lanes = 1 << u.log2Lanes, si = lane >> u.log2Lanes;
+  Lane L;
+  L.on = si < u.nSub;
+  L.lis = lane & ( lanes - 1 );
+  L.win = sPred + ( size_t ) wave * a.ldsPerWave + ( size_t ) si * subElems( u.tw, u.th, nt );
+  L.tmp = L.win + winElems( u.tw, u.th, nt );
+  const PredSub s = a.subs[u.firstSub + ( L.on ? si : 0 )];
+  const PredDev it = a.items[s.item];
+  const PredCiipDev ci = ciip[s.item];
+  L.ref[0] = it.ref[0]; L.ref[1] = it.ref[1]; L.stride[0] = it.stride[0]; L.stride[1] = it.stride[1];
+  L.fx[0] = it.frac[0][0]; L.fy[0] = it.frac[0][1]; L.fx[1] = it.frac[1][0]; L.fy[1] = it.frac[1][1];
+  L.w = it.w; L.h = it.h; L.alt = it.alt; L.x0 = s.x0; L.y0 = s.y0;
+  L.mode = it.ref[0] && it.ref[1] ? MODE_BI : MODE_UNI;
+  if( !it.ref[0] ) { L.ref[0] = it.ref[1]; L.stride[0] = it.stride[1]; L.fx[0] = L.fx[1]; L.fy[0] = L.fy[1]; L.ref[1] = nullptr; }      // a list-1-only block runs as the first pass
+  L.line = intraRef + ci.refOff; L.cw0 = ci.w0; L.cwI = ci.wI; L.cfilt = ci.filt; L.cpdpc = ci.pdpc;
+  L.dstPitch = a.predStride ? a.predStride : it.w;
+  L.dst = a.pred + it.dstOff;
+  L.org = a.org ? a.org + it.orgOff : nullptr; L.orgPitch = a.orgStride;
+  L.res = a.resi ? a.resi + it.dstOff : nullptr; L.resPitch = L.dstPitch;
+  predDispatchCiip( u.kind, L, u.tw, u.th, u.log2SegsRow, lanes, a.bitDepth );
+}
+
 // one block size per call, items on the device (the chroma twin of vvhip_interp_luma_batch): tile g of the launch is tile g % tilesPerItem of item g / tilesPerItem
 __global__ void __launch_bounds__( 256 )
 predOneSizeKernel( const int16_t* __restrict__ ref, int refStride, const vvhip_subpel_item* __restrict__ items, int n, int w, int h, int bitDepth, int rndRes,
@@ -654,12 +741,13 @@ const int8_t kBcwW1[5] = { -2, 3, 4, 5, 10 };      // g_BcwWeights (Rom.cpp:1152
 
 // validates the list, derives the schedule and uploads it; on success the context's key names the list (items + plane table) the device copy belongs to
 int predBuildSchedule( vvhip_ctx* ctx, vvhip_ctx::PredSched& S, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host,
-                       const vvhip_pred_blend* blend_host, int n, std::vector<unsigned char>& key )
+                       const vvhip_pred_blend* blend_host, const vvhip_pred_ciip* ciip_host, const int16_t* d_intra_ref, int n, std::vector<unsigned char>& key )
 {
   // ---- validation + plane table resolved; nothing is launched when any item is unsupported
   std::vector<PredDev> dev( n );
   std::vector<Keyed> order( n );
   std::vector<PredBlendDev> blendDev( blend_host ? n : 0 );
+  std::vector<PredCiipDev> ciipDev( ciip_host ? n : 0 );
   for( int i = 0; i < n; i++ )
   {
     const vvhip_pred_item& it = items_host[i];
@@ -739,8 +827,33 @@ int predBuildSchedule( vvhip_ctx* ctx, vvhip_ctx::PredSched& S, const vvhip_me_p
         blended = 1;
       }
     }
+    // ---- the CIIP record: a whole component block of a CIIP CU (luma 4..64 with w * h >= 64; 4:2:0 chroma 4..32 wide, 2..32 high, w * h >= 16: EncCu.cpp:1926, :2213-2219),
+    //      one list, the default average or BCW; no GEO, no BDOF / DMVR (InterPrediction.cpp:468, UnitTools.cpp:1309).  Such an item runs in the CIIP kernel whatever its blend record.
+    uint32_t ciipOn = 0;
+    if( ciip_host )
+    {
+      const vvhip_pred_ciip& c = ciip_host[i];
+      memset( &ciipDev[i], 0, sizeof( PredCiipDev ) );
+      if( c.mode > VVHIP_PRED_CIIP_ON || c.rsv[0] || c.rsv[1] )
+        return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ciip: item %d: unknown CIIP mode %d or non-zero reserved bytes", i, c.mode );
+      if( c.mode == VVHIP_PRED_CIIP_ON )
+      {
+        if( c.num_intra > 2 ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ciip: item %d: num_intra %d (0..2)", i, c.num_intra );
+        if( c.ref_off < 0 ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ciip: item %d: negative offset %d into the intra reference samples", i, c.ref_off );
+        if( !d_intra_ref ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ciip: item %d is a CIIP item and there are no intra reference samples", i );
+        const bool sizeOk = it.chroma ? ( it.width >= 4 && it.width <= 32 && it.height >= 2 && it.height <= 32 && it.width * it.height >= 16 )
+                                      : ( it.width >= 4 && it.width <= 64 && it.height >= 4 && it.height <= 64 && it.width * it.height >= 64 );
+        if( !sizeOk )
+          return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ciip: item %d: CIIP on a %s block %dx%d (luma 4..64 with w * h >= 64; chroma 4..32 wide, 2..32 high, w * h >= 16)", i, it.chroma ? "chroma" : "luma", it.width, it.height );
+        if( blend_host && blend_host[i].mode == VVHIP_PRED_BLEND_GEO ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ciip: item %d: CIIP excludes GEO", i );
+        if( flags ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ciip: item %d: CIIP excludes BDOF and DMVR's padded reference", i );
+        ciipDev[i].refOff = c.ref_off; ciipDev[i].w0 = ( int8_t ) ( blended ? blendDev[i].lo : 4 ); ciipDev[i].wI = ( uint8_t ) ( c.num_intra + 1 );
+        ciipDev[i].filt = it.chroma ? 0 : 1; ciipDev[i].pdpc = std::min( it.width, it.height ) >= 4 ? 1 : 0;
+        ciipOn = 1; blended = 0;
+      }
+    }
     // size class: the most samples first (their waves run longest), then shape, form, component and uni / bi — a wave never mixes classes; inside a class picture order
-    order[i].cls = ( ( uint32_t ) ( 14 - ilog2i( it.width ) - ilog2i( it.height ) ) << 9 ) | ( ( uint32_t ) ilog2i( it.width ) << 5 ) | ( blended << 4 ) | ( flags << 2 ) | ( it.chroma ? 2u : 0u ) | ( bi ? 1u : 0u );
+    order[i].cls = ( ( uint32_t ) ( 14 - ilog2i( it.width ) - ilog2i( it.height ) ) << 10 ) | ( ( uint32_t ) ilog2i( it.width ) << 6 ) | ( ciipOn << 5 ) | ( blended << 4 ) | ( flags << 2 ) | ( it.chroma ? 2u : 0u ) | ( bi ? 1u : 0u );
     const int l0 = it.ref_plane[0] >= 0 ? 0 : 1;
     order[i].pos = ( ( int64_t ) it.ref_off[l0] << 5 ) | ( uint32_t ) ( it.ref_plane[l0] & 31 );
     order[i].idx = i;
@@ -750,15 +863,15 @@ int predBuildSchedule( vvhip_ctx* ctx, vvhip_ctx::PredSched& S, const vvhip_me_p
   // ---- schedule: per class the tiles in picture order, 64 lanes' worth per wave, four waves per workgroup, workgroups dealt to the XCDs in bands
   //      classes with an extension flag go to a list of their own, which predListExKernel runs; a BDOF block is cut into its 16x16 / 16x8 / 8x16 units (xSubPuBDOF :326-357)
   std::vector<PredSub> subs;
-  std::vector<PredUnit> unitsPlain, unitsEx, unitsBlend;
-  int ldsPerWave = 0, ldsPerWaveEx = 0, ldsPerWaveBlend = 0;
+  std::vector<PredUnit> unitsPlain, unitsEx, unitsBlend, unitsCiip;
+  int ldsPerWave = 0, ldsPerWaveEx = 0, ldsPerWaveBlend = 0, ldsPerWaveCiip = 0;
   for( int c0 = 0; c0 < n; )
   {
     int c1 = c0; while( c1 < n && order[c1].cls == order[c0].cls ) c1++;
     const vvhip_pred_item& f = items_host[order[c0].idx];
     const uint32_t flags = ( order[c0].cls >> 2 ) & 3u;
-    const bool blended = ( order[c0].cls >> 4 ) & 1u;
-    std::vector<PredUnit>& units = blended ? unitsBlend : flags ? unitsEx : unitsPlain;
+    const bool blended = ( order[c0].cls >> 4 ) & 1u, ciipOn = ( order[c0].cls >> 5 ) & 1u;
+    std::vector<PredUnit>& units = ciipOn ? unitsCiip : blended ? unitsBlend : flags ? unitsEx : unitsPlain;
     TileShape ts = tileShape( f.width, f.height, f.chroma != 0 );
     if( flags & VVHIP_PRED_EXT_BDOF )
     {
@@ -766,7 +879,8 @@ int predBuildSchedule( vvhip_ctx* ctx, vvhip_ctx::PredSched& S, const vvhip_me_p
       ts.log2SegsRow = ilog2i( ts.tw / 8 ); ts.log2Lanes = ts.log2SegsRow + ilog2i( ts.th );
     }
     const int subsPerWave = 64 >> ts.log2Lanes, nt = tapsOfKind( ts.kind );
-    if( blended ) ldsPerWaveBlend = std::max( ldsPerWaveBlend, subsPerWave * subElems( ts.tw, ts.th, nt ) );
+    if( ciipOn ) ldsPerWaveCiip = std::max( ldsPerWaveCiip, subsPerWave * subElems( ts.tw, ts.th, nt ) );
+    else if( blended ) ldsPerWaveBlend = std::max( ldsPerWaveBlend, subsPerWave * subElems( ts.tw, ts.th, nt ) );
     else if( flags ) ldsPerWaveEx = std::max( ldsPerWaveEx, subsPerWave * ( subElems( ts.tw, ts.th, nt ) + ( ( flags & VVHIP_PRED_EXT_BDOF ) ? bdofElems( ts.tw, ts.th ) : 0 ) ) );
     else ldsPerWave = std::max( ldsPerWave, subsPerWave * subElems( ts.tw, ts.th, nt ) );
     const size_t firstSub = subs.size();
@@ -786,11 +900,13 @@ int predBuildSchedule( vvhip_ctx* ctx, vvhip_ctx::PredSched& S, const vvhip_me_p
   }
 
   // ---- device copy of the schedule: grow-only; the host copy stays alive as the source of the asynchronous upload
-  std::vector<PredUnit> units( unitsPlain );      // one table: the plain units, then the units of the extension kernel, then those of the blend kernel
+  std::vector<PredUnit> units( unitsPlain );      // one table: the plain units, then the units of the extension kernel, then those of the blend kernel, then those of the CIIP kernel
   units.insert( units.end(), unitsEx.begin(), unitsEx.end() );
   units.insert( units.end(), unitsBlend.begin(), unitsBlend.end() );
+  units.insert( units.end(), unitsCiip.begin(), unitsCiip.end() );
   const size_t bItems = ( dev.size() * sizeof( PredDev ) + 255 ) & ~( size_t ) 255, bSubs = ( subs.size() * sizeof( PredSub ) + 255 ) & ~( size_t ) 255;
-  const size_t bUnits = ( units.size() * sizeof( PredUnit ) + 255 ) & ~( size_t ) 255, bBlend = blendDev.size() * sizeof( PredBlendDev ), bAll = bItems + bSubs + bUnits + bBlend;
+  const size_t bUnits = ( units.size() * sizeof( PredUnit ) + 255 ) & ~( size_t ) 255, bBlend = blendDev.size() * sizeof( PredBlendDev ), bCiip = ciipDev.size() * sizeof( PredCiipDev );
+  const size_t bAll = bItems + bSubs + bUnits + bBlend + bCiip;
   if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipEventSynchronize( S.event ) );      // the last launch that reads the old schedule, whatever stream it went to
   S.key.clear();
   if( bAll > S.bytes )
@@ -806,17 +922,20 @@ int predBuildSchedule( vvhip_ctx* ctx, vvhip_ctx::PredSched& S, const vvhip_me_p
   memcpy( S.blob.data() + bItems, subs.data(), subs.size() * sizeof( PredSub ) );
   memcpy( S.blob.data() + bItems + bSubs, units.data(), units.size() * sizeof( PredUnit ) );
   if( bBlend ) memcpy( S.blob.data() + bItems + bSubs + bUnits, blendDev.data(), bBlend );
+  if( bCiip ) memcpy( S.blob.data() + bItems + bSubs + bUnits + bBlend, ciipDev.data(), bCiip );
   VVHIP_CHECK_HIP( ctx, hipMemcpyAsync( S.d_sched, S.blob.data(), S.blob.size(), hipMemcpyHostToDevice, ctx->stream ) );
   S.stream = ctx->stream;
   S.offSubs = bItems; S.offUnits = bItems + bSubs; S.offBlend = bItems + bSubs + bUnits; S.units = ( int ) unitsPlain.size(); S.ldsPerWave = ldsPerWave;
   S.unitsEx = ( int ) unitsEx.size(); S.ldsPerWaveEx = ldsPerWaveEx;
   S.unitsBlend = ( int ) unitsBlend.size(); S.ldsPerWaveBlend = ldsPerWaveBlend;
+  S.offCiip = S.offBlend + bBlend; S.unitsCiip = ( int ) unitsCiip.size(); S.ldsPerWaveCiip = ldsPerWaveCiip;
   S.key.swap( key );
   return VVHIP_OK;
 }
 
 int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host,
-                    const vvhip_pred_blend* blend_host, int n, int bit_depth, int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
+                    const vvhip_pred_blend* blend_host, const vvhip_pred_ciip* ciip_host, const int16_t* d_intra_ref, int n, int bit_depth, int16_t* d_pred, int pred_stride,
+                    const int16_t* d_org, int org_stride, int16_t* d_resi )
 {
   if( !ctx ) return VVHIP_E_ARG;
   if( !planes_host || n_planes < 1 || n_planes > 16 || n < 0 || n > ( 1 << 24 ) || bit_depth < 8 || bit_depth > 12 || pred_stride < 0 || ( n && ( !items_host || !d_pred ) ) || ( d_resi && !d_org ) )
@@ -829,18 +948,26 @@ int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_pla
 
   // ---- a list that is run again (same items, same plane table) is launched at once: no sort, no upload, no allocation, no wait — such a call can be recorded in a launch graph
   //      (the extensions are part of the list: the same items with other extensions are another schedule)
-  //      A list with a blend array keeps a schedule of its own (and its array is part of its key).
-  vvhip_ctx::PredSched& S = ctx->predSched[blend_host ? 1 : 0];
+  //      A list with a blend array keeps a schedule of its own (and its array is part of its key), and so does a list with a CIIP array.  The intra reference samples are
+  //      device data like the planes: their address and contents are not part of the key (the address is a kernel argument of every launch).
+  vvhip_ctx::PredSched& S = ctx->predSched[ciip_host ? 2 : blend_host ? 1 : 0];
   const size_t bKeyItems = sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ) + ( size_t ) n * sizeof( vvhip_pred_item ), bKeyExt = ext_host ? ( size_t ) n * sizeof( vvhip_pred_ext ) : 0;
-  std::vector<unsigned char> key( bKeyItems + bKeyExt + ( blend_host ? 1 + ( size_t ) n * sizeof( vvhip_pred_blend ) : 0 ) );
+  const size_t bKeyBlend = blend_host ? 1 + ( size_t ) n * sizeof( vvhip_pred_blend ) : 0;
+  std::vector<unsigned char> key( bKeyItems + bKeyExt + bKeyBlend + ( ciip_host ? 2 + ( size_t ) n * sizeof( vvhip_pred_ciip ) : 0 ) );
   if( ext_host ) memcpy( key.data() + bKeyItems, ext_host, bKeyExt );
   if( blend_host ) { key[bKeyItems + bKeyExt] = ext_host ? 1 : 0; memcpy( key.data() + bKeyItems + bKeyExt + 1, blend_host, ( size_t ) n * sizeof( vvhip_pred_blend ) ); }
+  if( ciip_host )
+  {
+    unsigned char* k = key.data() + bKeyItems + bKeyExt + bKeyBlend;
+    k[0] = ext_host ? 1 : 0; k[1] = blend_host ? 1 : 0;
+    memcpy( k + 2, ciip_host, ( size_t ) n * sizeof( vvhip_pred_ciip ) );
+  }
   memcpy( key.data(), &n_planes, sizeof( int ) );
   memcpy( key.data() + sizeof( int ), planes_host, ( size_t ) n_planes * sizeof( vvhip_me_plane ) );
   memcpy( key.data() + sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ), items_host, ( size_t ) n * sizeof( vvhip_pred_item ) );
   if( key != S.key )
   {
-    const int rc = predBuildSchedule( ctx, S, planes_host, n_planes, items_host, ext_host, blend_host, n, key );
+    const int rc = predBuildSchedule( ctx, S, planes_host, n_planes, items_host, ext_host, blend_host, ciip_host, d_intra_ref, n, key );
     if( rc ) return rc;
   }
   else if( S.stream != ctx->stream )      // same schedule, other stream: order it behind the upload
@@ -848,6 +975,7 @@ int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_pla
     if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipStreamWaitEvent( ctx->stream, S.event, 0 ) );
     S.stream = ctx->stream;
   }
+  if( S.unitsCiip && !d_intra_ref ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ciip: the list has CIIP items and there are no intra reference samples" );
   const size_t bItems = S.offSubs, bSubs = S.offUnits - S.offSubs;
   const int ldsPerWave = S.ldsPerWave, nUnits = S.units;
   PredArgs a;
@@ -873,6 +1001,13 @@ int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_pla
                         reinterpret_cast<const PredBlendDev*>( base + S.offBlend ) );
     VVHIP_LAUNCH_CHECK( ctx );
   }
+  if( S.unitsCiip )
+  {
+    a.units = reinterpret_cast<const PredUnit*>( base + bItems + bSubs ) + nUnits + S.unitsEx + S.unitsBlend; a.nUnits = S.unitsCiip; a.ldsPerWave = S.ldsPerWaveCiip;
+    hipLaunchKernelGGL( predListCiipKernel, dim3( ( unsigned ) ( a.nUnits / 4 ) ), dim3( 256 ), ( size_t ) a.ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a,
+                        reinterpret_cast<const PredCiipDev*>( base + S.offCiip ), d_intra_ref );
+    VVHIP_LAUNCH_CHECK( ctx );
+  }
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if( hipStreamIsCapturing( ctx->stream, &cap ) != hipSuccess ) cap = hipStreamCaptureStatusNone;
   if( cap == hipStreamCaptureStatusNone )      // (a launch recorded into a graph runs later: the graph's owner keeps the list unchanged while the graph is in use)
@@ -891,19 +1026,26 @@ extern "C" {
 int vvhip_pred_inter_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, int n, int bit_depth,
                             int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
 {
-  return predInterBatch( ctx, planes_host, n_planes, items_host, nullptr, nullptr, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
+  return predInterBatch( ctx, planes_host, n_planes, items_host, nullptr, nullptr, nullptr, nullptr, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
 }
 
 int vvhip_pred_inter_batch_ex( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host, int n, int bit_depth,
                                int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
 {
-  return predInterBatch( ctx, planes_host, n_planes, items_host, ext_host, nullptr, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
+  return predInterBatch( ctx, planes_host, n_planes, items_host, ext_host, nullptr, nullptr, nullptr, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
 }
 
 int vvhip_pred_inter_batch_blend( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host,
                                   const vvhip_pred_blend* blend_host, int n, int bit_depth, int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
 {
-  return predInterBatch( ctx, planes_host, n_planes, items_host, ext_host, blend_host, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
+  return predInterBatch( ctx, planes_host, n_planes, items_host, ext_host, blend_host, nullptr, nullptr, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
+}
+
+int vvhip_pred_inter_batch_ciip( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host,
+                                 const vvhip_pred_blend* blend_host, const vvhip_pred_ciip* ciip_host, const int16_t* d_intra_ref, int n, int bit_depth,
+                                 int16_t* d_pred, int pred_stride, const int16_t* d_org, int org_stride, int16_t* d_resi )
+{
+  return predInterBatch( ctx, planes_host, n_planes, items_host, ext_host, blend_host, ciip_host, d_intra_ref, n, bit_depth, d_pred, pred_stride, d_org, org_stride, d_resi );
 }
 
 int vvhip_get_geo_weights_host( int split_dir, int log2_cu_w, int log2_cu_h, int chroma, int8_t* host_out )

@@ -29,6 +29,8 @@ PRED_EXT_DTYPE = np.dtype([("flags", "u1"), ("pad_dx", "i1", (2,)), ("pad_dy", "
 PRED_EXT_BDOF, PRED_EXT_DMVR_PAD = 1, 2
 PRED_BLEND_DTYPE = np.dtype([("mode", "u1"), ("param", "u1"), ("rsv", "u1", (2,))])      # vvhip_pred_blend (4 bytes)
 PRED_BLEND_DEFAULT, PRED_BLEND_BCW, PRED_BLEND_GEO = 0, 1, 2      # param: - / bcw_idx 0..4 / geoSplitDir 0..63
+PRED_CIIP_DTYPE = np.dtype([("ref_off", "<i4"), ("mode", "u1"), ("num_intra", "u1"), ("rsv", "u1", (2,))])      # vvhip_pred_ciip (8 bytes)
+PRED_CIIP_OFF, PRED_CIIP_ON = 0, 1      # ON: ref_off = the block's line top[0 .. w + 2], left[0 .. h + 2] in intra_ref; num_intra 0..2
 PRED_AFFINE_ITEM_DTYPE = np.dtype([("dst_off", "<i4"), ("org_off", "<i4"), ("ref_off", "<i4", (2,)), ("cpmv", "<i4", (2, 3, 2)), ("cu_x", "<i2"), ("cu_y", "<i2"), ("cu_w", "<i2"),
                                    ("cu_h", "<i2"), ("ref_plane", "i1", (2,)), ("chroma", "u1"), ("six_param", "u1"), ("prof", "u1"), ("rsv", "u1", (3,))])      # vvhip_pred_affine_item (80 bytes)
 
@@ -567,14 +569,29 @@ class HotPath:
     class _MePlane(C.Structure):          # vvhip_me_plane
         _fields_ = [("d_base", C.c_void_p), ("stride", C.c_int32), ("reserved", C.c_int32)]
 
-    def pred_inter_batch(self, planes, items, pred, pred_stride=0, bit_depth=10, org=None, resi=None, ext=None, blend=None):
+    def pred_inter_batch(self, planes, items, pred, pred_stride=0, bit_depth=10, org=None, resi=None, ext=None, blend=None, ciip=None, intra_ref=None):
         """inter prediction of a list of prediction units in one launch: planes = the reference Planes the items' ref_plane indexes, items = PRED_ITEM_DTYPE records
         (HOST array: the library sorts it into size classes), pred = int16 tensor (compact blocks at dst_off, or a plane of row pitch pred_stride).
         org (a Plane) + resi (int16 tensor laid out like pred): also writes org - pred.
         ext = PRED_EXT_DTYPE records parallel to items (BDOF, DMVR's padded reference): vvhip_pred_inter_batch_ex.
-        blend = PRED_BLEND_DTYPE records parallel to items (BCW weights, GEO partitions): vvhip_pred_inter_batch_blend, with ext or without."""
+        blend = PRED_BLEND_DTYPE records parallel to items (BCW weights, GEO partitions): vvhip_pred_inter_batch_blend, with ext or without.
+        ciip = PRED_CIIP_DTYPE records parallel to items (planar intra part and weighting of CIIP CUs) + intra_ref = int16 DEVICE tensor of the reference-sample lines
+        they point into: vvhip_pred_inter_batch_ciip, with ext / blend or without."""
         it = np.ascontiguousarray(items, PRED_ITEM_DTYPE)
         tab = (self._MePlane * max(1, len(planes)))(*[self._MePlane(p.buf_ptr.value, p.stride, 0) for p in planes])
+        if ciip is not None:
+            ci = np.ascontiguousarray(ciip, PRED_CIIP_DTYPE)
+            ex = np.ascontiguousarray(ext, PRED_EXT_DTYPE) if ext is not None else None
+            bl = np.ascontiguousarray(blend, PRED_BLEND_DTYPE) if blend is not None else None
+            if ci.size != it.size or (ex is not None and ex.size != it.size) or (bl is not None and bl.size != it.size):
+                raise ValueError("pred_inter_batch: %d CIIP records, %s extensions, %s blend records for %d items"
+                                 % (ci.size, "no" if ex is None else ex.size, "no" if bl is None else bl.size, it.size))
+            self._ck(self.L.vvhip_pred_inter_batch_ciip(self.ctx, C.cast(tab, C.c_void_p), len(planes), it.ctypes.data_as(C.c_void_p) if it.size else None,
+                                                        ex.ctypes.data_as(C.c_void_p) if ex is not None and ex.size else None,
+                                                        bl.ctypes.data_as(C.c_void_p) if bl is not None and bl.size else None,
+                                                        ci.ctypes.data_as(C.c_void_p) if ci.size else None, _ptr(intra_ref), int(it.size), bit_depth, _ptr(pred), pred_stride,
+                                                        org.buf_ptr if org is not None else None, org.stride if org is not None else 0, _ptr(resi)))
+            return pred
         if blend is not None:
             bl = np.ascontiguousarray(blend, PRED_BLEND_DTYPE)
             ex = np.ascontiguousarray(ext, PRED_EXT_DTYPE) if ext is not None else None

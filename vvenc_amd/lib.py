@@ -87,6 +87,7 @@ PROTOTYPES = {
     "vvhip_pred_inter_batch": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, vp, i32, vp]),
     "vvhip_pred_inter_batch_ex": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, i32, vp, i32, vp]),
     "vvhip_pred_inter_batch_blend": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp]),
+    "vvhip_pred_inter_batch_ciip": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp]),
     "vvhip_pred_affine_batch": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp]),
     "vvhip_subpel_dist_batch": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "vvhip_mctf_apply_plane": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, C.c_double, C.c_double, vp, i32]),
