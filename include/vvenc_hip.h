@@ -280,6 +280,56 @@ VVHIP_API int vvhip_tu_rdo_multi_strided( vvhip_ctx* ctx, const int16_t* d_resi,
  * written.  An all-zero tile then moves 2 w h bytes in and 24 bytes per TU out instead of 6 w h + 24.                                                                          */
 VVHIP_API int vvhip_tu_set_sparse_outputs( vvhip_ctx* ctx, int on );
 
+/* Joint Cb-Cr residual coding (ICT) around the fused TU pipeline: the detour every chroma TU with a coded block flag takes in InterSearch::xEstimateInterResidualQT
+ * (EncoderLib/InterSearch.cpp:3770-3960) — TrQuant::selectICTCandidates -> fwdTransformICT (CommonLib/TrQuant.cpp:350-410), ONE pass of the joint residual through
+ * transform / quantisation / dequantisation / inverse transform, invTransformICT (:358-362), two SSEs — as two list entries, so that a picture's chroma residuals stay on the
+ * device: forward, then vvhip_tu_rdo_multi_strided on the joint buffer, then inverse.  The arithmetic is fwdTransformCbCr / invTransformCbCr (TrQuant.cpp:95-164), bit-exact
+ * for ANY int16 input.  mode = the signed ICT mode g_ictModes[jointCbCrSign][cbfMask] (Rom.cpp:1453: { 0, 3, 1, 2 } / { 0, -3, -1, -2 }; TU::getICTMode), computed by the caller.
+ *   forward, per sample with cb, cr widened to int ( / truncates toward zero; the quotient is narrowed to int16 as Pel( ... ) does, wrapping at the extremes; the distortion
+ *   uses the narrowed value; ( -c ) >> 1 is an arithmetic shift of the negated int; sums are int64 ):
+ *     mode +-1 : c = ( 4 cb +- 2 cr ) / 5,  d1 += ( cb - c )^2 + ( cr - ( ( +-c ) >> 1 ) )^2
+ *     mode +-2 : c = ( cb +- cr ) / 2,      d1 += ( cb - c )^2 + ( cr -+ c )^2
+ *     mode +-3 : c = ( 4 cr +- 2 cb ) / 5,  d1 += ( cb - ( ( +-c ) >> 1 ) )^2 + ( cr - c )^2
+ *     mode 0   : no joint block,            d1 = sum cb^2, d2 = sum cr^2            ( d2 = 0 for the other modes )
+ *   inverse: the joint reconstruction IS the coded component — Cb for |mode| = 1, 2, Cr for |mode| = 3 — and the other one is derived, narrowed to int16:
+ *     mode +-1 : cr = ( +-cb ) >> 1        mode +-2 : cr = +-cb        mode +-3 : cb = ( +-cr ) >> 1
+ *   item      : one chroma TU.  Its Cb and Cr blocks sit at cb_off / cr_off (sample offsets) with row pitch stride — in d_resi for the forward entry, in d_rec and
+ *               d_org_resi for the inverse entry: the reconstruction mirrors the residual layout, as d_resi mirrors d_pred in the prediction lists (compact blocks, or two
+ *               planes of one buffer).  The joint block is COMPACT (row pitch = width) at joint_off: d_joint is directly a d_resi of vvhip_tu_rdo_multi_strided with
+ *               resi_strides_host[i] = width, and that job's d_rec_resi a d_joint_rec.  width / height independent powers of two, 2..64.
+ *   forward   : writes the joint block (mode != 0) and d_dist[2i], d_dist[2i + 1] = ( d1, d2 ).  Several items may name the same Cb / Cr pair with different modes — the four
+ *               masks selectICTCandidates tests for an intra CU — and the host selection (TrQuant.cpp:377-407) is fed from d_dist.
+ *   inverse   : writes both components to d_rec and d_sse[2i], d_sse[2i + 1] = the plain sums of squared differences of the Cb / Cr reconstruction against d_org_resi —
+ *               unweighted and without precision shift, like vvhip_tu_stats.sse (the chroma distortion weight of RdCost::getDistPart stays with the caller).
+ *               With stats_idx >= 0 and d_stats[stats_idx].abs_sum == 0 the joint reconstruction is taken as ALL ZERO and d_joint_rec is not read for that item: the reference
+ *               fills the block with zero there (InterSearch.cpp:3896-3899), and the sparse outputs of vvhip_tu_set_sparse_outputs leave that memory unspecified — with the
+ *               TU job's statistics named here the chain runs with sparse outputs on.
+ * items_host is a HOST array, like the prediction lists': the library sorts it into size classes (a wave never mixes shapes; small blocks share a wave — sixteen 4x4 or
+ * thirty-two 2x2 blocks), and keeps the device copy of that schedule in the context, per entry and apart from the prediction entries' — the same list again uploads and
+ * allocates nothing, and alternating with the prediction entries evicts none of their schedules.  Results do not depend on the order of the list; nothing outside the named
+ * blocks is written; every access is a vector access as wide as the block's offsets, pitch and width and the buffers' addresses allow (16 bytes at best); every sum is
+ * reduced inside one wave and stored once — no atomics, so the results are deterministic.  Output blocks of different items must not overlap.
+ * Argument errors (VVHIP_E_ARG with a message naming the entry, nothing launched): n < 0; a size that is not a power of two in 2..64; stride < width; a negative offset;
+ * mode outside -3..3; mode 0 in the inverse entry; non-zero rsv; a needed pointer that is NULL (d_resi; d_joint with any mode != 0; d_joint_rec; d_org_resi with d_sse);
+ * stats_idx >= 0 with d_stats == NULL.
+ * NOT done here (the caller's job): CABAC bit estimation and the lambda scaling of the joint mode (InterSearch.cpp:3846-3853), chroma transform skip candidates, the chroma
+ * distortion weight.                                                                                                                                                       */
+typedef struct
+{
+  int32_t cb_off, cr_off;   /* the TU's Cb / Cr block: sample offsets, row pitch `stride`                       */
+  int32_t stride;
+  int32_t joint_off;        /* the joint block, COMPACT (row pitch = width)                                      */
+  int32_t stats_idx;        /* inverse only: index into d_stats, -1 = none                                       */
+  int16_t width, height;    /* independent powers of two, 2..64                                                  */
+  int8_t  mode;             /* signed ICT mode, -3..3                                                            */
+  uint8_t rsv[3];           /* zero                                                                              */
+} vvhip_ict_item;           /* 28 bytes */
+VVHIP_API int vvhip_ict_fwd_batch( vvhip_ctx* ctx, const int16_t* d_resi, const vvhip_ict_item* items_host, int n,
+                                   int16_t* d_joint /* may be NULL if every mode is 0 */, int64_t* d_dist /* 2 per item, may be NULL */ );
+VVHIP_API int vvhip_ict_inv_batch( vvhip_ctx* ctx, const int16_t* d_joint_rec, const vvhip_ict_item* items_host, int n,
+                                   const vvhip_tu_stats* d_stats /* may be NULL */, int16_t* d_rec /* may be NULL */,
+                                   const int16_t* d_org_resi /* may be NULL */, uint64_t* d_sse /* 2 per item: Cb, Cr; may be NULL */ );
+
 /* ---- the g_tCoeffOps table slots one-to-one (CommonLib/TrQuant_EMT.h:63-91), device pointers, caller's matrix ------------------
  * vvhip_fast_fwd_core  <- fastFwdCore_2D/_1D[log2(tr_size)-2]  (TrQuant_EMT.cpp:1973-2000):
  *     dst[j*line + i] = ( sum_k src[i*tr_size + k] * tc[j*tr_size + k] + 2^(shift-1) ) >> shift,  i < reduced_line, j < cutoff

@@ -66,6 +66,19 @@ struct vvhip_ctx
   hipStream_t  affStream  = nullptr;
   hipEvent_t   affEvent   = nullptr;
   bool         affEventRecorded = false;
+  // the same for the joint Cb-Cr entries (ict.hip): [0] vvhip_ict_fwd_batch, [1] vvhip_ict_inv_batch — each a schedule (sorted items + wave units), key, host copy and event
+  // of its own, apart from the prediction entries' slots: alternating with them on one context evicts nothing
+  struct IctSched
+  {
+    void*        d_sched   = nullptr;
+    size_t       bytes     = 0;
+    std::vector<unsigned char> key, blob;
+    size_t       offUnits  = 0;
+    int          units     = 0;
+    hipStream_t  stream    = nullptr;      // the stream the schedule was uploaded on; compared only, never used as a handle
+    hipEvent_t   event     = nullptr;      // recorded behind every launch that reads the schedule
+    bool         eventRecorded = false;
+  } ictSched[2];
   // how the host waits for the stream (vvhip_set_blocking_sync): false = hipStreamSynchronize (the runtime's low-latency wait), true = a blocking event — the calling thread
   // sleeps, which matters when the host's cores are all busy encoding
   bool         blockingSync = false;

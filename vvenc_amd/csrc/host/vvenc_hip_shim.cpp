@@ -869,6 +869,115 @@ bool DMVROps::refineCu( const Pel* ref0, int stride0, int fx0, int fy0, const Pe
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------ JointCbCrOps
+bool JointCbCrOps::codeList( const Tu* tus, int n, int bitDepth, bool isIRAP, TCoeff thrVal, int64_t* dist, TCoeffSig* levels, Pel* recCb, Pel* recCr, vvhip_tu_stats* stats,
+                             uint64_t* sse )
+{
+  if( n < 0 || ( n && !tus ) ) return false;
+  if( n == 0 ) return true;
+  Device& dev = Device::get();
+  const bool chain = levels || recCb || recCr || stats || sse;
+  // ---- the list: residuals compact (Cb block, Cr block per TU), joint blocks compact and grouped by size — one TU job per size, its TUs in list order
+  std::vector<vvhip_ict_item> items( n );
+  std::vector<size_t> outOff( n );      // where a TU's block starts in the caller's compact outputs
+  std::vector<int> order( n );
+  for( int i = 0; i < n; i++ ) order[i] = i;
+  std::stable_sort( order.begin(), order.end(), [tus]( int a, int b ) { return tus[a].width != tus[b].width ? tus[a].width > tus[b].width : tus[a].height > tus[b].height; } );
+  size_t resiElems = 0, jointElems = 0;
+  for( int i = 0; i < n; i++ )
+  {
+    const Tu& t = tus[i];
+    if( !t.cb || !t.cr || t.width < 2 || t.height < 2 || t.width > 64 || t.height > 64 ) throw Exception( "JointCbCrOps::codeList: TU " + std::to_string( i ) + " has no blocks or a size outside 2..64" );
+    memset( &items[i], 0, sizeof( vvhip_ict_item ) );
+    items[i].cb_off = ( int32_t ) resiElems; items[i].cr_off = ( int32_t ) ( resiElems + ( size_t ) t.width * t.height ); items[i].stride = t.width;
+    items[i].width = ( int16_t ) t.width; items[i].height = ( int16_t ) t.height; items[i].mode = ( int8_t ) t.mode; items[i].stats_idx = -1;
+    outOff[i] = resiElems / 2;
+    resiElems += 2 * ( size_t ) t.width * t.height;
+  }
+  std::vector<vvhip_tu_job> jobs;
+  std::vector<int32_t> strides, offs( n );
+  std::vector<vvhip_tu_qp> qps( n );
+  for( int k = 0; k < n; k++ )
+  {
+    const int i = order[k];
+    const Tu& t = tus[i];
+    items[i].joint_off = ( int32_t ) jointElems; items[i].stats_idx = chain ? k : -1;
+    offs[k] = ( int32_t ) jointElems; qps[k].qp = ( int16_t ) t.qp; qps[k].flags = ( int16_t ) ( isIRAP ? 1 : 0 );      // (bit 1 clear: chroma)
+    if( k == 0 || tus[order[k - 1]].width != t.width || tus[order[k - 1]].height != t.height )
+    {
+      vvhip_tu_job j; memset( &j, 0, sizeof( j ) );
+      j.width = t.width; j.height = t.height; j.tr_hor = 0; j.tr_ver = 0; j.n = 0; j.thr_val = ( int32_t ) thrVal;
+      jobs.push_back( j ); strides.push_back( t.width );
+    }
+    jobs.back().n++;
+    if( t.mode != 0 ) jointElems += ( size_t ) t.width * t.height;
+    else if( chain ) throw Exception( "JointCbCrOps::codeList: TU " + std::to_string( i ) + " has ICT mode 0: the chain codes joint blocks only" );
+  }
+  // ---- device memory: [ residual | joint | levels | joint reconstruction | reconstruction ] samples, [ offsets | qps | stats | dist | sse ] records
+  auto pad = []( size_t elems ) { return ( elems + 127 ) & ~( size_t ) 127; };
+  const size_t eResi = pad( resiElems ), eJoint = pad( jointElems ? jointElems : 1 );
+  int16_t* dResi = dev.staging( ( 2 * eResi + 3 * eJoint ) * sizeof( Pel ) + 256 );
+  int16_t* dJoint = dResi + eResi; int16_t* dLevel = dJoint + eJoint; int16_t* dJointRec = dLevel + eJoint; int16_t* dRec = dJointRec + eJoint;
+  const size_t bOffs = ( ( size_t ) n * 4 + 255 ) & ~( size_t ) 255, bQps = bOffs, bStats = ( ( size_t ) n * sizeof( vvhip_tu_stats ) + 255 ) & ~( size_t ) 255, bSums = ( ( size_t ) n * 16 + 255 ) & ~( size_t ) 255;
+  char* aux = static_cast<char*>( dev.stagingAux( bOffs + bQps + bStats + 2 * bSums + 256 ) );
+  int32_t* dOffs = reinterpret_cast<int32_t*>( aux ); vvhip_tu_qp* dQps = reinterpret_cast<vvhip_tu_qp*>( aux + bOffs );
+  vvhip_tu_stats* dStats = reinterpret_cast<vvhip_tu_stats*>( aux + bOffs + bQps );
+  int64_t* dDist = reinterpret_cast<int64_t*>( aux + bOffs + bQps + bStats ); uint64_t* dSse = reinterpret_cast<uint64_t*>( aux + bOffs + bQps + bStats + bSums );
+  std::vector<Pel> host( resiElems );
+  for( int i = 0; i < n; i++ )
+    for( int c = 0; c < 2; c++ )
+    {
+      const Pel* src = c ? tus[i].cr : tus[i].cb;
+      Pel* dst = host.data() + ( c ? items[i].cr_off : items[i].cb_off );
+      for( int y = 0; y < tus[i].height; y++ ) memcpy( dst + ( size_t ) y * tus[i].width, src + ( ptrdiff_t ) y * tus[i].stride, sizeof( Pel ) * tus[i].width );
+    }
+  dev.check( vvhip_upload( dev.ctx(), dResi, host.data(), resiElems * sizeof( Pel ) ), "joint Cb-Cr residuals" );
+  dev.check( vvhip_ict_fwd_batch( dev.ctx(), dResi, items.data(), n, jointElems ? dJoint : nullptr, dist ? dDist : nullptr ), "vvhip_ict_fwd_batch" );
+  if( chain )
+  {
+    dev.check( vvhip_upload( dev.ctx(), dOffs, offs.data(), ( size_t ) n * 4 ), "joint TU offsets" );
+    dev.check( vvhip_upload( dev.ctx(), dQps, qps.data(), ( size_t ) n * sizeof( vvhip_tu_qp ) ), "joint TU quantiser parameters" );
+    int first = 0;
+    for( vvhip_tu_job& j : jobs )
+    {
+      j.d_resi_off = dOffs + first; j.d_qp = dQps + first; j.d_level = dLevel + offs[first]; j.d_rec_resi = dJointRec + offs[first]; j.d_stats = dStats + first;
+      first += j.n;
+    }
+    dev.check( vvhip_tu_rdo_multi_strided( dev.ctx(), dJoint, strides.data(), bitDepth, jobs.data(), ( int ) jobs.size() ), "vvhip_tu_rdo_multi_strided" );
+    dev.check( vvhip_ict_inv_batch( dev.ctx(), dJointRec, items.data(), n, dStats, ( recCb || recCr ) ? dRec : nullptr, sse ? dResi : nullptr, sse ? dSse : nullptr ), "vvhip_ict_inv_batch" );
+  }
+  // ---- results back, in list order
+  if( dist ) dev.check( vvhip_download( dev.ctx(), dist, dDist, ( size_t ) n * 16 ), "joint Cb-Cr pair distortions" );
+  if( !chain ) return true;
+  if( sse ) dev.check( vvhip_download( dev.ctx(), sse, dSse, ( size_t ) n * 16 ), "joint Cb-Cr SSEs" );
+  std::vector<vvhip_tu_stats> st( n );
+  dev.check( vvhip_download( dev.ctx(), st.data(), dStats, ( size_t ) n * sizeof( vvhip_tu_stats ) ), "joint TU statistics" );
+  if( stats ) for( int k = 0; k < n; k++ ) stats[order[k]] = st[k];
+  if( levels )
+  {
+    std::vector<Pel> lv( jointElems );
+    dev.check( vvhip_download( dev.ctx(), lv.data(), dLevel, jointElems * sizeof( Pel ) ), "joint TU levels" );
+    for( int k = 0; k < n; k++ )
+    {
+      const int i = order[k];
+      const size_t cnt = ( size_t ) tus[i].width * tus[i].height;
+      if( st[k].abs_sum ) memcpy( levels + outOff[i], lv.data() + offs[k], cnt * sizeof( Pel ) );      // (sparse outputs leave the levels of a TU without any unspecified)
+      else memset( levels + outOff[i], 0, cnt * sizeof( Pel ) );
+    }
+  }
+  if( recCb || recCr )
+  {
+    dev.check( vvhip_download( dev.ctx(), host.data(), dRec, resiElems * sizeof( Pel ) ), "joint Cb-Cr reconstructions" );
+    for( int i = 0; i < n; i++ )
+    {
+      const size_t cnt = ( size_t ) tus[i].width * tus[i].height;
+      if( recCb ) memcpy( recCb + outOff[i], host.data() + items[i].cb_off, cnt * sizeof( Pel ) );
+      if( recCr ) memcpy( recCr + outOff[i], host.data() + items[i].cr_off, cnt * sizeof( Pel ) );
+    }
+  }
+  return true;
+}
+
 // ------------------------------------------------------------------------------------------------ InterPredOps
 bool InterPredOps::predictList( const Pel* const* refPlanes, int numPlanes, const vvhip_pred_item* items, int n, int bitDepth, Pel* pred, size_t predElems, const Pel* org, Pel* resi,
                                 const vvhip_pred_ext* ext, const vvhip_pred_blend* blend, const vvhip_pred_ciip* ciip, const Pel* intraRef, size_t intraRefElems )

@@ -219,6 +219,28 @@ struct QuantOps
                              const int defaultQuantisationCoefficient, const int iQBits, const int64_t iAdd, const TCoeff thrVal, const int lfnstIdx );
 };
 
+// Joint Cb-Cr residual coding of a LIST of chroma TUs in one device chain (vvhip_ict_fwd_batch -> vvhip_tu_rdo_multi_strided -> vvhip_ict_inv_batch): what
+// InterSearch::xEstimateInterResidualQT does per chroma TU around TrQuant::fwdTransformICT / transformNxN / invTransformNxN / invTransformICT
+// (EncoderLib/InterSearch.cpp:3770-3960, CommonLib/TrQuant.cpp:95-164, :350-410).  Host blocks in, host results out; nothing but the list crosses twice.
+struct JointCbCrOps
+{
+  struct Tu
+  {
+    const Pel* cb; const Pel* cr;      // the TU's two residual blocks, row pitch `stride`
+    int stride, width, height;         // width / height independent powers of two, 2..64
+    int mode;                          // signed ICT mode g_ictModes[jointCbCrSign][cbfMask] (Rom.cpp:1453), -3..3
+    int qp;                            // the joint block's QpParam::Qp (chroma scale)
+  };
+  // dist (2 per TU): the pair distortion ( d1, d2 ) of fwdTransformICT, for every mode including 0 — a candidate list (the four masks selectICTCandidates tests on one
+  // Cb / Cr pair are four Tus) is this call with every other output nullptr: only the forward entry runs.
+  // With any other output the whole chain runs and every mode must be non-zero.  Outputs are compact, TU after TU in list order (row pitch = width): levels = the joint
+  // block's quantised levels, recCb / recCr = both reconstructed residuals, stats = the joint TU's vvhip_tu_stats (abs_sum == 0: levels and reconstructions are zero),
+  // sse (2 per TU) = the plain SSEs of recCb / recCr against cb / cr.  Any of them may be nullptr.  Transform DCT-2 both ways, as the chroma TU of an inter CU has it.
+  // false: an argument this method itself rejects (n < 0, no TUs array); throws like every table entry when the device rejects the list.
+  bool codeList( const Tu* tus, int n, int bitDepth, bool isIRAP, TCoeff thrVal, int64_t* dist, TCoeffSig* levels = nullptr, Pel* recCb = nullptr, Pel* recCr = nullptr,
+                 vvhip_tu_stats* stats = nullptr, uint64_t* sse = nullptr );
+};
+
 // DMVR refinement search of one CU in one device call (DMVR::xProcessDMVR, CommonLib/InterPrediction.cpp:1262-1392).
 // What to do with the result: sub-blocks whose refinement is zero (and every PU that is not refined at all) can go straight into a prediction list
 // (InterPredOps::predictList: luma and chroma, both lists, the average); a sub-block with a non-zero refinement goes into the same list with an extension record

@@ -72,6 +72,25 @@ def dmvr_pred_items(results, start_mv, pos, ref_planes, strides, dx, dy, bdof=Tr
             e["flags"] = fl
     return items, ext
 STATS_DTYPE = np.dtype([("abs_sum", "<i4"), ("last_scan_pos", "<i4"), ("need_rdoq", "<i4"), ("pad", "<i4"), ("sse", "<u8")])
+ICT_ITEM_DTYPE = np.dtype([("cb_off", "<i4"), ("cr_off", "<i4"), ("stride", "<i4"), ("joint_off", "<i4"), ("stats_idx", "<i4"), ("width", "<i2"), ("height", "<i2"),
+                           ("mode", "i1"), ("rsv", "u1", (3,))])      # vvhip_ict_item (28 bytes)
+ICT_MODES = ((0, 3, 1, 2), (0, -3, -1, -2))      # g_ictModes[jointCbCrSign][cbfMask] (Rom.cpp:1453)
+
+
+def make_ict_items(blocks):
+    """the joint Cb-Cr items of a list of chroma TUs: blocks = (cb_off, cr_off, stride, width, height, mode) each -> (items, samples of the joint buffer): ICT_ITEM_DTYPE
+    records with stats_idx = -1 and the joint blocks laid out compactly, grouped by size in list order inside a size — the blocks of one size are then one compact TU job
+    (d_resi_off = their joint_off, pitch = width) whose compact reconstruction of n * w * h samples lands at the same offsets.  Items of mode 0 code no joint block."""
+    it = np.zeros(len(blocks), ICT_ITEM_DTYPE)
+    for k, (cb, cr, stride, w, h, mode) in enumerate(blocks):
+        it[k]["cb_off"], it[k]["cr_off"], it[k]["stride"], it[k]["width"], it[k]["height"], it[k]["mode"], it[k]["stats_idx"] = cb, cr, stride, w, h, mode, -1
+    at = 0
+    for w, h in sorted({(int(i["width"]), int(i["height"])) for i in it}, reverse=True):
+        for k in range(len(it)):
+            if (int(it[k]["width"]), int(it[k]["height"])) == (w, h) and int(it[k]["mode"]) != 0:
+                it[k]["joint_off"] = at
+                at += w * h
+    return it, at
 
 
 def _ptr(t):
@@ -412,6 +431,66 @@ class HotPath:
             jobs = self.make_tu_jobs(jobs)
         arr = (C.c_int32 * len(strides))(*strides)
         self._ck(self.L.vvhip_tu_rdo_multi_strided(self.ctx, _ptr(d_resi), C.cast(arr, C.c_void_p), bit_depth, jobs[0], jobs[1]))
+
+    # ---- joint Cb-Cr residual coding (ICT) around the TU lists ----
+    def ict_fwd_batch(self, resi, items, joint=None, dist=None):
+        """vvhip_ict_fwd_batch: resi = int16 DEVICE tensor holding the Cb / Cr residual blocks, items = ICT_ITEM_DTYPE records (HOST array), joint = int16 tensor for the compact
+        joint blocks (None only if every mode is 0), dist = int64 tensor [n, 2] for the pair distortions ( d1, d2 ) or None."""
+        it = np.ascontiguousarray(items, ICT_ITEM_DTYPE)
+        self._ck(self.L.vvhip_ict_fwd_batch(self.ctx, _ptr(resi), it.ctypes.data_as(C.c_void_p) if it.size else None, int(it.size), _ptr(joint), _ptr(dist)))
+        return joint, dist
+
+    def ict_inv_batch(self, joint_rec, items, stats=None, rec=None, org_resi=None, sse=None):
+        """vvhip_ict_inv_batch: joint_rec = int16 DEVICE tensor of the compact joint reconstructions, stats = the TU job's statistics the items' stats_idx index (or None),
+        rec = int16 tensor laid out like the residual (both components are written) or None, org_resi + sse = the original residuals and a uint64-sized tensor [n, 2]
+        (torch.int64 storage) for the Cb / Cr SSEs, or None."""
+        it = np.ascontiguousarray(items, ICT_ITEM_DTYPE)
+        self._ck(self.L.vvhip_ict_inv_batch(self.ctx, _ptr(joint_rec), it.ctypes.data_as(C.c_void_p) if it.size else None, int(it.size), _ptr(stats), _ptr(rec), _ptr(org_resi),
+                                            _ptr(sse)))
+        return rec, sse
+
+    def make_joint_tu_jobs(self, items, qps, irap=0, tr_hor=DCT2, tr_ver=DCT2, thr_val=8):
+        """the TU jobs of the joint blocks of make_ict_items' items (all modes non-zero): one job per size, its TUs in list order, reading the joint buffer at the items'
+        joint_off (pitch = width) and reconstructing to the same offsets of a second buffer; qps = the joint QP per item (chroma scale).  Sets the items' stats_idx.
+        -> (items, jobs, strides, level, joint_rec, stats): a make_tu_jobs list with the per-job pitches, and the three output buffers the jobs' tensors are views of."""
+        it = np.ascontiguousarray(items, ICT_ITEM_DTYPE).copy()
+        total = int(max((int(i["joint_off"]) + int(i["width"]) * int(i["height"]) for i in it), default=0))
+        level, joint_rec = (torch.zeros(max(total, 1), dtype=torch.int16, device=self.device) for _ in range(2))
+        stats = torch.zeros((max(len(it), 1), STATS_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        qps = np.broadcast_to(np.asarray(qps), (len(it),))
+        jobs, strides, first = [], [], 0
+        for w, h in sorted({(int(i["width"]), int(i["height"])) for i in it}, reverse=True):
+            ks = [k for k in range(len(it)) if (int(it[k]["width"]), int(it[k]["height"])) == (w, h)]
+            offs = it["joint_off"][ks].astype(np.int32)
+            base = int(offs[0])
+            if not np.array_equal(offs, base + w * h * np.arange(len(ks), dtype=np.int32)):
+                raise ValueError("make_joint_tu_jobs: the %dx%d joint blocks are not one compact run in list order (make_ict_items lays them out so)" % (w, h))
+            it["stats_idx"][ks] = first + np.arange(len(ks))
+            jobs.append((w, h, tr_hor, tr_ver, len(ks), thr_val, self.to_device(offs), self.to_device(self.tu_qp(qps[ks], irap, 0)),
+                         level[base:base + len(ks) * w * h], joint_rec[base:base + len(ks) * w * h], stats[first:first + len(ks)]))
+            strides.append(w)
+            first += len(ks)
+        return it, jobs, strides, level, joint_rec, stats
+
+    def tu_rdo_joint(self, resi, items, jobs, strides, joint_rec, stats, bit_depth=10, joint=None, dist=None, rec=None, sse=None):
+        """the joint chroma chain of a picture's TUs on the device: ict_fwd_batch -> tu_rdo_multi_strided on the joint buffer -> ict_inv_batch (with the jobs' statistics,
+        so it holds with sparse outputs on).  resi = int16 DEVICE tensor with the Cb / Cr residuals; items, jobs, strides, joint_rec, stats as make_joint_tu_jobs returns them
+        (jobs a list or a prepared make_tu_jobs table).  -> (joint, dist, rec, sse): the joint residuals, the pair distortions [n, 2], the two reconstructed components in the
+        layout of resi (elsewhere zero when allocated here), the SSEs [n, 2] (Cb, Cr) against resi."""
+        it = np.ascontiguousarray(items, ICT_ITEM_DTYPE)
+        n = int(it.size)
+        if joint is None:
+            joint = torch.empty_like(joint_rec)
+        if dist is None:
+            dist = torch.empty((n, 2), dtype=torch.int64, device=self.device)
+        if rec is None:
+            rec = torch.zeros_like(resi)
+        if sse is None:
+            sse = torch.empty((n, 2), dtype=torch.int64, device=self.device)
+        self.ict_fwd_batch(resi, it, joint, dist)
+        self.tu_rdo_multi_strided(joint, strides, jobs, bit_depth)
+        self.ict_inv_batch(joint_rec, it, stats, rec, resi, sse)
+        return joint, dist, rec, sse
 
     # ---- motion-search plans: integer candidates + sub-pel stages + plain table calls of a picture in one launch ----
     def me_plan_create(self, int_jobs, cands, stage_jobs, items, bit_depth=10, max_window=0, mask_items=None):

@@ -117,6 +117,8 @@ PROTOTYPES = {
     "vvhip_mctf_motion_estimation": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "vvhip_mctf_motion_estimation_async": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "vvhip_tu_set_sparse_outputs": (i32, [vp, i32]),
+    "vvhip_ict_fwd_batch": (i32, [vp, vp, vp, i32, vp, vp]),
+    "vvhip_ict_inv_batch": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
     "vvhip_mctf_set_stats": (i32, [vp, i32]),
     "vvhip_mctf_get_stats": (i32, [vp, vp]),
     "vvhip_mctf_set_timing": (i32, [vp, i32]),
