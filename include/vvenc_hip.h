@@ -330,6 +330,89 @@ VVHIP_API int vvhip_ict_inv_batch( vvhip_ctx* ctx, const int16_t* d_joint_rec, c
                                    const vvhip_tu_stats* d_stats /* may be NULL */, int16_t* d_rec /* may be NULL */,
                                    const int16_t* d_org_resi /* may be NULL */, uint64_t* d_sse /* 2 per item: Cb, Cr; may be NULL */ );
 
+/* Sub-block transform (SBT) around the fused TU pipeline: the one residual tool of inter CUs that codes only ONE HALF or ONE QUARTER of the CU's residual, with
+ * position-dependent DST-7 / DCT-8, and takes the rest as zero (InterSearch::xEstimateInterResidualQT with cu.sbtInfo; on in the reference's slow, slower and medium-low
+ * presets).  A coded tile is an ordinary TU job on a sub-rectangle of the CU's residual — vvhip_tu_rdo_multi_strided reads it in place — so there are three pieces, all
+ * data-parallel over a picture's CU list: parts, tiles, placement.  4:2:0 only: the chroma blocks are half size.
+ * SBT mode 0..7 = SBT_VER_H0, SBT_VER_H1, SBT_HOR_H0, SBT_HOR_H1, SBT_VER_Q0, SBT_VER_Q1, SBT_HOR_Q0, SBT_HOR_Q1 (CommonLib/TypeDef.h:284-291) = 2 ( sbtIdx - 1 ) + sbtPos.
+ * sbt_allowed = what CU::checkAllowedSbt returns (CommonLib/UnitTools.cpp:249-268): bit 1 SBT_VER_HALF (width >= 8), bit 2 SBT_HOR_HALF (height >= 8), bit 3 SBT_VER_QUAD
+ * (width >= 16), bit 4 SBT_HOR_QUAD (height >= 16) — carried by the item and not derived, because the encoder also clears bits by picture width and size (EncCu.cpp:3797).
+ *
+ * vvhip_sbt_parts_batch = InterSearch::xCalcMinDistSbt (EncoderLib/InterSearch.cpp:3272-3464) for a list of CUs, bit for bit.  The CU's Y, Cb and Cr residual blocks sit at
+ * y_off / cb_off / cr_off (sample offsets into d_resi) with row pitches stride_y / stride_c; org - pred of the reference IS that residual, and with
+ * DISTORTION_PRECISION_ADJUSTMENT 0 (TypeDef.h:171) no bit depth is needed.  width / height (luma) independent powers of two, 4..64.  Every output pointer may be NULL:
+ *   d_parts[n][3][16] : the UNWEIGHTED sum of squares of every part per component (Y, Cb, Cr), row-major [j][i] in a 4 x 4 frame; the grid has numPartX = width >= 16 ? 4 :
+ *                       width == 4 ? 1 : 2 columns, rows likewise (:3291-3292); a chroma part is ( width / 2 ) / numPartX x ( height / 2 ) / numPartY, down to 2 x 2.
+ *                       Cells outside the grid are zero.
+ *   d_est[n][9]       : m_estMinDistSbt[0..8] as :3338-3425 leaves it — [8] the CU's total, a mode whose type is not allowed MAX_DISTORTION (all ones), the halves
+ *                       ( resi >> 5 ) + noResi, the quads sum( own + ( others << 5 ) ) >> 5.  Every component's part sum is weighted on its own before the components are
+ *                       added: luma as it is, chroma (uint64)( double( sum ) * chroma_weight ) — one IEEE multiplication, truncated toward zero (:3329-3333);
+ *                       chroma_weight = RdCost::getChromaWeight() (RdCost.h:166).
+ *   d_order[n][8]     : m_sbtRdoOrder as :3427-3463 leaves it — the min( 2 x allowed half types, SBT_NUM_RDO = 2 ) best half modes, then likewise the quad modes; strict <,
+ *                       so a tie goes to the lower mode; unused entries 255.
+ * NOT done here (the caller's job): items with sbt_allowed == 0 are an argument error — their plain SSE is a distortion list's; "fast algorithm 1" (:3353-3359,
+ * m_skipSbtAll) needs lambda and is one comparison on d_est[i][8]; skipSbtByRDCost, the history-based initSbtRdoOrder and every CABAC bit.
+ *
+ * vvhip_sbt_tiles (host arithmetic, no context, nothing launched) = CU::getSbtTuSplit (UnitTools.cpp:3388), PartitionerImpl::getSbtTuTiling (CommonLib/UnitPartitioner.cpp:
+ * 995-1056) and the SBT branch of TrQuant::xSetTrTypes (CommonLib/TrQuant.cpp:435-466): out[c], c = Y, Cb, Cr, is the CODED tile of the component block — tile 0 for
+ * position 0, tile 1 for position 1 — with the factors ( dim * f ) >> 2 per component: where it lies inside the block ( x, y, width, height ), resi_off = the sample offset of
+ * its corner and stride = the CU's pitch: one TU of a vvhip_tu_rdo_multi_strided job reads it in place.  The uncoded quad tile is three quarters of the CU, not a power of two,
+ * and never transformed.  Luma types: vertical split DCT-8 / DST-7 (hor / ver) at position 0 and DST-7 / DST-7 at position 1, horizontal split DST-7 / DCT-8 at position 0
+ * and DST-7 / DST-7 at position 1; DCT-2 / DCT-2 when the tile's side ALONG the split line — the height of a vertical split's tile, the width of a horizontal split's —
+ * exceeds MTS_INTER_MAX_CU_SIZE (32); chroma always DCT-2.  Returns VVHIP_E_ARG for a mode outside 0..7, a size that is not a power of two in 4..64, a half mode on a side
+ * below 8 or a quad mode on a side below 16.
+ *
+ * vvhip_sbt_place_batch: one item per CANDIDATE.  The CU's three blocks sit at y_off / cb_off / cr_off in d_rec and d_org_resi (the layout of the residual); per component
+ * the compact reconstruction of the coded tile (row pitch = the tile's width: a TU job's d_rec_resi) sits at tile_off[c] in d_tile_rec, and stats_idx[c] names the TU's
+ * statistics in d_stats.  Per component the entry writes the WHOLE block of d_rec — the coded tile from d_tile_rec, the other tile zero (tu.noResidual, InterSearch.cpp:3562,
+ * :3758-3762) — and d_sse[3i + c] = the plain sum of squared differences of that block against d_org_resi, unweighted and unshifted like vvhip_tu_stats.sse: the tile's SSE
+ * plus the energy of the zeroed part.  stats_idx[c] >= 0 with d_stats[stats_idx[c]].abs_sum == 0: the tile is ALL ZERO and d_tile_rec is not read, so the chain holds with
+ * vvhip_tu_set_sparse_outputs on; stats_idx[c] == -1: the caller dropped that component's coefficients (cbf 0) — zero as well, tile_off[c] is ignored.
+ *
+ * Both list entries follow the joint Cb-Cr entries: items_host is a HOST array, sorted by the library into size classes (a wave never mixes classes, small CUs share a wave);
+ * the device copy of that schedule stays in the context in slots of its own — the same list again uploads and allocates nothing, and alternating with the joint Cb-Cr and
+ * prediction entries evicts none of theirs.  Accesses are vectors as wide as offsets, pitches, part / tile widths and base addresses allow (2..16 bytes); every sum is 64-bit,
+ * reduced inside one wave and stored once — no atomics: results do not depend on the order of the list.  Nothing outside the named blocks is written.  Output blocks of
+ * different items must not overlap.
+ * Argument errors (VVHIP_E_ARG with a message naming the entry, nothing launched): n < 0; a size that is not a power of two in 4..64; a pitch below the width; a negative
+ * offset; sbt_allowed == 0, or with a bit the size cannot have (bits outside 1..4, half types on a side below 8, quad types on a side below 16); non-zero rsv; a needed
+ * pointer that is NULL (d_resi; d_org_resi with d_sse; d_stats or d_tile_rec with any stats_idx >= 0); a misaligned array; placement: mode outside 0..7, a mode whose type
+ * bit is not in sbt_allowed, stats_idx below -1, a negative tile offset.
+ * NOT done here (the caller's job): m_skipSbtAll, skipSbtByRDCost, the history order, bits and lambda, the chroma distortion weight of getDistPart, SBT combined with the MTS
+ * candidates of the unsplit TU, 4:2:2 and 4:4:4.                                                                                                                            */
+typedef struct
+{
+  int32_t y_off, cb_off, cr_off;   /* the CU's Y / Cb / Cr block: sample offsets                                  */
+  int32_t stride_y, stride_c;      /* row pitches of the luma block and of both chroma blocks                     */
+  int16_t width, height;           /* luma; independent powers of two, 4..64                                      */
+  uint8_t sbt_allowed;             /* CU::checkAllowedSbt's bits, non-zero                                        */
+  uint8_t rsv[3];                  /* zero                                                                        */
+} vvhip_sbt_item;                  /* 28 bytes */
+typedef struct
+{
+  int32_t resi_off, stride;        /* the coded tile's corner in the buffer of the CU's blocks, the CU's pitch    */
+  int16_t x, y, width, height;     /* the coded tile inside the component block                                   */
+  int8_t  tr_hor, tr_ver;          /* VVHIP_DCT2 / VVHIP_DCT8 / VVHIP_DST7                                        */
+  uint8_t rsv[2];
+} vvhip_sbt_tile;                  /* 20 bytes */
+typedef struct
+{
+  int32_t y_off, cb_off, cr_off;   /* the CU's blocks in d_rec and d_org_resi                                     */
+  int32_t stride_y, stride_c;
+  int32_t tile_off[3];             /* per component: the coded tile's COMPACT reconstruction in d_tile_rec        */
+  int32_t stats_idx[3];            /* per component: index into d_stats, -1 = no coefficients (all zero)          */
+  int16_t width, height;
+  uint8_t sbt_allowed;
+  uint8_t mode;                    /* SBT mode 0..7                                                               */
+  uint8_t rsv[2];                  /* zero                                                                        */
+} vvhip_sbt_place_item;            /* 52 bytes */
+VVHIP_API int vvhip_sbt_parts_batch( vvhip_ctx* ctx, const int16_t* d_resi, const vvhip_sbt_item* items_host, int n, double chroma_weight,
+                                     uint64_t* d_parts /* n x 3 x 16, may be NULL */, uint64_t* d_est /* n x 9, may be NULL */, uint8_t* d_order /* n x 8, may be NULL */ );
+VVHIP_API int vvhip_sbt_tiles( const vvhip_sbt_item* cu, int mode, vvhip_sbt_tile* out /* 3: Y, Cb, Cr */ );
+VVHIP_API int vvhip_sbt_place_batch( vvhip_ctx* ctx, const int16_t* d_tile_rec /* may be NULL if no stats_idx >= 0 */, const vvhip_sbt_place_item* items_host, int n,
+                                     const vvhip_tu_stats* d_stats /* may be NULL */, int16_t* d_rec /* may be NULL */,
+                                     const int16_t* d_org_resi /* may be NULL */, uint64_t* d_sse /* 3 per item: Y, Cb, Cr; may be NULL */ );
+
 /* ---- the g_tCoeffOps table slots one-to-one (CommonLib/TrQuant_EMT.h:63-91), device pointers, caller's matrix ------------------
  * vvhip_fast_fwd_core  <- fastFwdCore_2D/_1D[log2(tr_size)-2]  (TrQuant_EMT.cpp:1973-2000):
  *     dst[j*line + i] = ( sum_k src[i*tr_size + k] * tc[j*tr_size + k] + 2^(shift-1) ) >> shift,  i < reduced_line, j < cutoff

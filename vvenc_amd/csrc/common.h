@@ -79,6 +79,9 @@ struct vvhip_ctx
     hipEvent_t   event     = nullptr;      // recorded behind every launch that reads the schedule
     bool         eventRecorded = false;
   } ictSched[2];
+  // the same for the sub-block transform entries (sbt.hip): [0] vvhip_sbt_parts_batch, [1] vvhip_sbt_place_batch — slots of their own again, so that alternating them with the
+  // joint Cb-Cr and the prediction entries on one context evicts none of theirs
+  IctSched sbtSched[2];
   // how the host waits for the stream (vvhip_set_blocking_sync): false = hipStreamSynchronize (the runtime's low-latency wait), true = a blocking event — the calling thread
   // sleeps, which matters when the host's cores are all busy encoding
   bool         blockingSync = false;

@@ -260,6 +260,11 @@ void vvhip_destroy( vvhip_ctx* ctx )
     if( S.d_sched ) ( void ) hipFree( S.d_sched );
     if( S.event ) ( void ) hipEventDestroy( S.event );
   }
+  for( vvhip_ctx::IctSched& S : ctx->sbtSched )
+  {
+    if( S.d_sched ) ( void ) hipFree( S.d_sched );
+    if( S.event ) ( void ) hipEventDestroy( S.event );
+  }
   if( ctx->d_affSched ) ( void ) hipFree( ctx->d_affSched );
   if( ctx->affEvent ) ( void ) hipEventDestroy( ctx->affEvent );
   if( ctx->d_mctfStats ) ( void ) hipFree( ctx->d_mctfStats );

@@ -2,6 +2,7 @@
 #include "vvenc_hip_shim.h"
 
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
@@ -973,6 +974,172 @@ bool JointCbCrOps::codeList( const Tu* tus, int n, int bitDepth, bool isIRAP, TC
       const size_t cnt = ( size_t ) tus[i].width * tus[i].height;
       if( recCb ) memcpy( recCb + outOff[i], host.data() + items[i].cb_off, cnt * sizeof( Pel ) );
       if( recCr ) memcpy( recCr + outOff[i], host.data() + items[i].cr_off, cnt * sizeof( Pel ) );
+    }
+  }
+  return true;
+}
+
+// ------------------------------------------------------------------------------------------------ SbtOps
+bool SbtOps::codeList( const Cu* cus, int nCus, const Cand* cands, int nCands, double chromaWeight, int bitDepth, bool isIRAP, TCoeff thrVal, uint64_t* parts, uint64_t* est,
+                       uint8_t* order, TCoeffSig* levels, Pel* rec, vvhip_tu_stats* stats, uint64_t* sse )
+{
+  if( nCus < 0 || nCands < 0 || ( nCus && !cus ) || ( nCands && !cands ) ) return false;
+  if( nCus == 0 ) return true;
+  Device& dev = Device::get();
+  auto pad = []( size_t elems ) { return ( elems + 127 ) & ~( size_t ) 127; };
+  // ---- the CU list: residuals compact (Y, Cb, Cr block per CU)
+  std::vector<vvhip_sbt_item> items( nCus );
+  size_t resiElems = 0;
+  for( int i = 0; i < nCus; i++ )
+  {
+    const Cu& c = cus[i];
+    if( !c.y || !c.cb || !c.cr || c.width < 4 || c.height < 4 || c.width > 64 || c.height > 64 ) throw Exception( "SbtOps::codeList: CU " + std::to_string( i ) + " has no blocks or a size outside 4..64" );
+    vvhip_sbt_item& it = items[i];
+    memset( &it, 0, sizeof( it ) );
+    const size_t aY = ( size_t ) c.width * c.height;
+    it.y_off = ( int32_t ) resiElems; it.cb_off = ( int32_t ) ( resiElems + aY ); it.cr_off = ( int32_t ) ( resiElems + aY + aY / 4 );
+    it.stride_y = c.width; it.stride_c = c.width / 2; it.width = ( int16_t ) c.width; it.height = ( int16_t ) c.height; it.sbt_allowed = ( uint8_t ) c.sbtAllowed;
+    resiElems += aY + aY / 2;
+  }
+  // ---- the candidates: one TU per component, grouped into jobs by ( width, height, types, pitch ), a job's TUs in list order; candidates of one CU share its block of the
+  // reconstruction, so the r-th candidate of every CU is placed into plane r
+  struct TuRef { int cand, comp; int32_t resiOff; };
+  struct Key { int w, h, th, tv, stride; bool operator<( const Key& o ) const { return std::tie( o.w, o.h, o.th, o.tv, o.stride ) < std::tie( w, h, th, tv, stride ); } };      // widest first
+  std::map<Key, std::vector<TuRef>> groups;
+  std::vector<vvhip_sbt_place_item> place( nCands );
+  std::vector<int> planeOf( nCands ), seen( nCus, 0 );
+  std::vector<std::array<vvhip_sbt_tile, 3>> tiles( nCands );
+  int planes = 0;
+  for( int k = 0; k < nCands; k++ )
+  {
+    const Cand& cd = cands[k];
+    if( cd.cu < 0 || cd.cu >= nCus ) throw Exception( "SbtOps::codeList: candidate " + std::to_string( k ) + " names CU " + std::to_string( cd.cu ) );
+    const vvhip_sbt_item& it = items[cd.cu];
+    if( vvhip_sbt_tiles( &it, cd.mode, tiles[k].data() ) != VVHIP_OK ) throw Exception( "SbtOps::codeList: candidate " + std::to_string( k ) + ": SBT mode " + std::to_string( cd.mode ) + " does not fit its CU" );
+    vvhip_sbt_place_item& p = place[k];
+    memset( &p, 0, sizeof( p ) );
+    p.y_off = it.y_off; p.cb_off = it.cb_off; p.cr_off = it.cr_off; p.stride_y = it.stride_y; p.stride_c = it.stride_c; p.width = it.width; p.height = it.height;
+    p.sbt_allowed = it.sbt_allowed; p.mode = ( uint8_t ) cd.mode;
+    for( int c = 0; c < 3; c++ )
+    {
+      const vvhip_sbt_tile& t = tiles[k][c];
+      groups[Key{ t.width, t.height, t.tr_hor, t.tr_ver, t.stride }].push_back( TuRef{ k, c, t.resi_off } );
+    }
+    planeOf[k] = seen[cd.cu]++;
+    planes = std::max( planes, planeOf[k] + 1 );
+  }
+  const int nTus = 3 * nCands;
+  std::vector<vvhip_tu_job> jobs;
+  std::vector<int32_t> strides, offs;
+  std::vector<vvhip_tu_qp> qps;
+  std::vector<size_t> jobBase;
+  size_t tileElems = 0;
+  for( const auto& g : groups )
+  {
+    tileElems = ( tileElems + 7 ) & ~( size_t ) 7;      // a job's compact outputs start 16-byte aligned
+    vvhip_tu_job j; memset( &j, 0, sizeof( j ) );
+    j.width = g.first.w; j.height = g.first.h; j.tr_hor = g.first.th; j.tr_ver = g.first.tv; j.n = ( int32_t ) g.second.size(); j.thr_val = ( int32_t ) thrVal;
+    jobs.push_back( j ); strides.push_back( g.first.stride ); jobBase.push_back( tileElems );
+    for( size_t q = 0; q < g.second.size(); q++ )
+    {
+      const TuRef& r = g.second[q];
+      place[r.cand].tile_off[r.comp] = ( int32_t ) ( tileElems + q * ( size_t ) j.width * j.height ); place[r.cand].stats_idx[r.comp] = ( int32_t ) offs.size();
+      offs.push_back( r.resiOff );
+      vvhip_tu_qp qp; qp.qp = ( int16_t ) cands[r.cand].qp[r.comp]; qp.flags = ( int16_t ) ( ( isIRAP ? 1 : 0 ) | ( r.comp == 0 ? 2 : 0 ) );
+      qps.push_back( qp );
+    }
+    tileElems += g.second.size() * ( size_t ) j.width * j.height;
+  }
+  // ---- device memory: [ residual | levels | tile reconstructions | one reconstruction plane per round ] samples, [ offsets | qps | stats | parts | est | order | sse ] records
+  const size_t eResi = pad( resiElems ), eTiles = pad( tileElems ? tileElems : 1 );
+  int16_t* dResi = dev.staging( ( eResi * ( 1 + ( size_t ) planes ) + 2 * eTiles ) * sizeof( Pel ) + 256 );
+  int16_t* dLevel = dResi + eResi; int16_t* dTileRec = dLevel + eTiles; int16_t* dRec = dTileRec + eTiles;
+  auto pad256 = []( size_t b ) { return ( b + 255 ) & ~( size_t ) 255; };
+  const size_t bOffs = pad256( ( size_t ) nTus * 4 + 4 ), bStats = pad256( ( size_t ) nTus * sizeof( vvhip_tu_stats ) + 8 ), bParts = pad256( ( size_t ) nCus * 48 * 8 ), bEst = pad256( ( size_t ) nCus * 9 * 8 ),
+               bOrder = pad256( ( size_t ) nCus * 8 ), bSse = pad256( ( size_t ) nCands * 3 * 8 + 8 );
+  char* aux = static_cast<char*>( dev.stagingAux( 2 * bOffs + bStats + bParts + bEst + bOrder + bSse + 256 ) );
+  int32_t* dOffs = reinterpret_cast<int32_t*>( aux ); vvhip_tu_qp* dQps = reinterpret_cast<vvhip_tu_qp*>( aux + bOffs );
+  vvhip_tu_stats* dStats = reinterpret_cast<vvhip_tu_stats*>( aux + 2 * bOffs );
+  uint64_t* dParts = reinterpret_cast<uint64_t*>( aux + 2 * bOffs + bStats ); uint64_t* dEst = reinterpret_cast<uint64_t*>( aux + 2 * bOffs + bStats + bParts );
+  uint8_t* dOrder = reinterpret_cast<uint8_t*>( aux + 2 * bOffs + bStats + bParts + bEst ); uint64_t* dSse = reinterpret_cast<uint64_t*>( aux + 2 * bOffs + bStats + bParts + bEst + bOrder );
+  std::vector<Pel> host( resiElems );
+  for( int i = 0; i < nCus; i++ )
+    for( int c = 0; c < 3; c++ )
+    {
+      const Pel* src = c == 0 ? cus[i].y : c == 1 ? cus[i].cb : cus[i].cr;
+      const int w = cus[i].width >> ( c ? 1 : 0 ), h = cus[i].height >> ( c ? 1 : 0 ), stride = c ? cus[i].strideC : cus[i].strideY;
+      Pel* dst = host.data() + ( c == 0 ? items[i].y_off : c == 1 ? items[i].cb_off : items[i].cr_off );
+      for( int y = 0; y < h; y++ ) memcpy( dst + ( size_t ) y * w, src + ( ptrdiff_t ) y * stride, sizeof( Pel ) * w );
+    }
+  dev.check( vvhip_upload( dev.ctx(), dResi, host.data(), resiElems * sizeof( Pel ) ), "SBT residuals" );
+  if( parts || est || order )
+  {
+    dev.check( vvhip_sbt_parts_batch( dev.ctx(), dResi, items.data(), nCus, chromaWeight, parts ? dParts : nullptr, est ? dEst : nullptr, order ? dOrder : nullptr ), "vvhip_sbt_parts_batch" );
+    if( parts ) dev.check( vvhip_download( dev.ctx(), parts, dParts, ( size_t ) nCus * 48 * 8 ), "SBT part sums" );
+    if( est ) dev.check( vvhip_download( dev.ctx(), est, dEst, ( size_t ) nCus * 9 * 8 ), "SBT estimates" );
+    if( order ) dev.check( vvhip_download( dev.ctx(), order, dOrder, ( size_t ) nCus * 8 ), "SBT order" );
+  }
+  if( nCands == 0 || !( levels || rec || stats || sse ) ) return true;
+  dev.check( vvhip_upload( dev.ctx(), dOffs, offs.data(), ( size_t ) nTus * 4 ), "SBT tile offsets" );
+  dev.check( vvhip_upload( dev.ctx(), dQps, qps.data(), ( size_t ) nTus * sizeof( vvhip_tu_qp ) ), "SBT tile quantiser parameters" );
+  int first = 0;
+  for( size_t q = 0; q < jobs.size(); q++ )
+  {
+    vvhip_tu_job& j = jobs[q];
+    j.d_resi_off = dOffs + first; j.d_qp = dQps + first; j.d_level = dLevel + jobBase[q]; j.d_rec_resi = dTileRec + jobBase[q]; j.d_stats = dStats + first;
+    first += j.n;
+  }
+  dev.check( vvhip_tu_rdo_multi_strided( dev.ctx(), dResi, strides.data(), bitDepth, jobs.data(), ( int ) jobs.size() ), "vvhip_tu_rdo_multi_strided" );
+  std::vector<vvhip_tu_stats> st( nTus );
+  dev.check( vvhip_download( dev.ctx(), st.data(), dStats, ( size_t ) nTus * sizeof( vvhip_tu_stats ) ), "SBT tile statistics" );
+  if( stats ) for( int k = 0; k < nCands; k++ ) for( int c = 0; c < 3; c++ ) stats[3 * k + c] = st[place[k].stats_idx[c]];
+  // where a candidate's blocks start in the caller's compact outputs
+  std::vector<size_t> recOff( nCands ), levOff( nCands );
+  size_t recElems = 0, levElems = 0;
+  for( int k = 0; k < nCands; k++ )
+  {
+    recOff[k] = recElems; levOff[k] = levElems;
+    recElems += ( size_t ) place[k].width * place[k].height * 3 / 2;
+    for( int c = 0; c < 3; c++ ) levElems += ( size_t ) tiles[k][c].width * tiles[k][c].height;
+  }
+  if( levels )
+  {
+    std::vector<Pel> lv( tileElems );
+    dev.check( vvhip_download( dev.ctx(), lv.data(), dLevel, tileElems * sizeof( Pel ) ), "SBT tile levels" );
+    for( int k = 0; k < nCands; k++ )
+    {
+      size_t at = levOff[k];
+      for( int c = 0; c < 3; c++ )
+      {
+        const size_t cnt = ( size_t ) tiles[k][c].width * tiles[k][c].height;
+        if( st[place[k].stats_idx[c]].abs_sum ) memcpy( levels + at, lv.data() + place[k].tile_off[c], cnt * sizeof( Pel ) );      // (sparse outputs leave the levels of a TU without any unspecified)
+        else memset( levels + at, 0, cnt * sizeof( Pel ) );
+        at += cnt;
+      }
+    }
+  }
+  if( rec || sse )
+  {
+    std::vector<vvhip_sbt_place_item> round;
+    std::vector<int> who;
+    std::vector<uint64_t> s;
+    for( int r = 0; r < planes; r++ )
+    {
+      round.clear(); who.clear();
+      for( int k = 0; k < nCands; k++ ) if( planeOf[k] == r ) { round.push_back( place[k] ); who.push_back( k ); }
+      dev.check( vvhip_sbt_place_batch( dev.ctx(), dTileRec, round.data(), ( int ) round.size(), dStats, rec ? dRec + ( size_t ) r * eResi : nullptr, sse ? dResi : nullptr, sse ? dSse : nullptr ),
+                 "vvhip_sbt_place_batch" );
+      if( sse )
+      {
+        s.resize( 3 * round.size() );
+        dev.check( vvhip_download( dev.ctx(), s.data(), dSse, s.size() * 8 ), "SBT SSEs" );
+        for( size_t q = 0; q < who.size(); q++ ) for( int c = 0; c < 3; c++ ) sse[3 * who[q] + c] = s[3 * q + c];
+      }
+      if( rec )
+      {
+        dev.check( vvhip_download( dev.ctx(), host.data(), dRec + ( size_t ) r * eResi, resiElems * sizeof( Pel ) ), "SBT reconstructions" );
+        for( int k : who ) memcpy( rec + recOff[k], host.data() + place[k].y_off, ( size_t ) place[k].width * place[k].height * 3 / 2 * sizeof( Pel ) );      // ( Y, Cb, Cr are adjacent )
+      }
     }
   }
   return true;

@@ -241,6 +241,33 @@ struct JointCbCrOps
                  vvhip_tu_stats* stats = nullptr, uint64_t* sse = nullptr );
 };
 
+// Sub-block transform (SBT) of a LIST of inter CUs in one device chain (vvhip_sbt_parts_batch -> vvhip_tu_rdo_multi_strided on the coded tiles -> vvhip_sbt_place_batch): what
+// InterSearch::xCalcMinDistSbt computes per CU before any candidate is coded (EncoderLib/InterSearch.cpp:3272-3464) and what xEstimateInterResidualQT does per SBT
+// candidate around transformNxN / invTransformNxN — the tiling of PartitionerImpl::getSbtTuTiling, the types of TrQuant::xSetTrTypes, the uncoded tile zero.
+// Host blocks in, host results out.
+struct SbtOps
+{
+  struct Cu
+  {
+    const Pel* y; const Pel* cb; const Pel* cr;      // the CU's three residual blocks (4:2:0), row pitches strideY / strideC
+    int strideY, strideC, width, height;             // luma width / height: independent powers of two, 4..64
+    int sbtAllowed;                                  // CU::checkAllowedSbt's bits (after the encoder's own clearing), non-zero
+  };
+  struct Cand
+  {
+    int cu;                                          // index into the CU list
+    int mode;                                        // SBT mode 0..7 = 2 ( sbtIdx - 1 ) + sbtPos (TypeDef.h:284-291)
+    int qp[3];                                       // QpParam::Qp of Y, Cb, Cr
+  };
+  // Per CU: parts (3 x 16: the unweighted part sums), est (9: m_estMinDistSbt), order (8: m_sbtRdoOrder) — a call with nCands == 0 runs the parts entry alone.
+  // Per candidate, in list order: levels = the coded tile's quantised levels of Y, Cb, Cr one after the other (compact, row pitch = the tile's width), rec = the CU's
+  // three reconstructed residual blocks one after the other (compact, row pitch = the block's width; the uncoded tile zero), stats (3) = the tiles' vvhip_tu_stats
+  // (abs_sum == 0: levels and reconstruction are zero), sse (3) = the plain SSEs of the three blocks against the CU's residual.  Any output may be nullptr.
+  // false: an argument this method itself rejects (negative counts, no arrays); throws like every table entry when the device rejects a list.
+  bool codeList( const Cu* cus, int nCus, const Cand* cands, int nCands, double chromaWeight, int bitDepth, bool isIRAP, TCoeff thrVal, uint64_t* parts, uint64_t* est,
+                 uint8_t* order, TCoeffSig* levels = nullptr, Pel* rec = nullptr, vvhip_tu_stats* stats = nullptr, uint64_t* sse = nullptr );
+};
+
 // DMVR refinement search of one CU in one device call (DMVR::xProcessDMVR, CommonLib/InterPrediction.cpp:1262-1392).
 // What to do with the result: sub-blocks whose refinement is zero (and every PU that is not refined at all) can go straight into a prediction list
 // (InterPredOps::predictList: luma and chroma, both lists, the average); a sub-block with a non-zero refinement goes into the same list with an extension record

@@ -93,6 +93,56 @@ def make_ict_items(blocks):
     return it, at
 
 
+SBT_ITEM_DTYPE = np.dtype([("y_off", "<i4"), ("cb_off", "<i4"), ("cr_off", "<i4"), ("stride_y", "<i4"), ("stride_c", "<i4"), ("width", "<i2"), ("height", "<i2"),
+                           ("sbt_allowed", "u1"), ("rsv", "u1", (3,))])      # vvhip_sbt_item (28 bytes)
+SBT_TILE_DTYPE = np.dtype([("resi_off", "<i4"), ("stride", "<i4"), ("x", "<i2"), ("y", "<i2"), ("width", "<i2"), ("height", "<i2"), ("tr_hor", "i1"), ("tr_ver", "i1"),
+                           ("rsv", "u1", (2,))])      # vvhip_sbt_tile (20 bytes)
+SBT_PLACE_DTYPE = np.dtype([("y_off", "<i4"), ("cb_off", "<i4"), ("cr_off", "<i4"), ("stride_y", "<i4"), ("stride_c", "<i4"), ("tile_off", "<i4", (3,)), ("stats_idx", "<i4", (3,)),
+                            ("width", "<i2"), ("height", "<i2"), ("sbt_allowed", "u1"), ("mode", "u1"), ("rsv", "u1", (2,))])      # vvhip_sbt_place_item (52 bytes)
+SBT_VER_HALF, SBT_HOR_HALF, SBT_VER_QUAD, SBT_HOR_QUAD = 1, 2, 3, 4      # SbtIdx (TypeDef.h:266-270): the bits of sbt_allowed; SBT mode = 2 * ( idx - 1 ) + pos
+SBT_MAX_DIST = (1 << 64) - 1      # MAX_DISTORTION: the estimate of a mode whose type is not allowed
+
+
+def sbt_allowed_of(w, h):
+    """CU::checkAllowedSbt's size rule (UnitTools.cpp:256-267): halves from a side of 8, quads from a side of 16"""
+    return ((w >= 8) << SBT_VER_HALF) | ((h >= 8) << SBT_HOR_HALF) | ((w >= 16) << SBT_VER_QUAD) | ((h >= 16) << SBT_HOR_QUAD)
+
+
+def make_sbt_items(cus):
+    """the SBT items of a list of CUs: cus = (y_off, cb_off, cr_off, stride_y, stride_c, width, height, sbt_allowed) each -> SBT_ITEM_DTYPE records"""
+    it = np.zeros(len(cus), SBT_ITEM_DTYPE)
+    for k, cu in enumerate(cus):
+        for name, v in zip(("y_off", "cb_off", "cr_off", "stride_y", "stride_c", "width", "height", "sbt_allowed"), cu):
+            it[k][name] = v
+    return it
+
+
+def sbt_coded_tile(w, h, mode):
+    """the coded tile (x, y, width, height) of a w x h component block: getSbtTuTiling's factors ( dim * f ) >> 2 (UnitPartitioner.cpp:995-1056); tile 0 for position 0,
+    tile 1 for position 1"""
+    ver, quad, pos1 = ((mode >> 1) & 1) == 0, mode >= 4, mode & 1
+    side = w if ver else h
+    length, at = (side * (1 if quad else 2)) >> 2, ((side * (3 if quad else 2)) >> 2) if pos1 else 0
+    return (at, 0, length, h) if ver else (0, at, w, length)
+
+
+def sbt_tiles(item, mode):
+    """the Python mirror of vvhip_sbt_tiles: the coded tile of each component (Y, Cb, Cr) of one SBT_ITEM_DTYPE record as SBT_TILE_DTYPE records — where it lies, the offset of
+    its corner, the CU's pitch and the luma transform types of TrQuant::xSetTrTypes' SBT branch (TrQuant.cpp:435-466); chroma is DCT-2"""
+    W, H = int(item["width"]), int(item["height"])
+    ver, quad, pos1 = ((mode >> 1) & 1) == 0, mode >= 4, mode & 1
+    if not 0 <= mode <= 7 or (W if ver else H) < (16 if quad else 8):
+        raise ValueError("sbt_tiles: SBT mode %d on a %dx%d CU" % (mode, W, H))
+    out = np.zeros(3, SBT_TILE_DTYPE)
+    for c, (off, stride) in enumerate(((item["y_off"], item["stride_y"]), (item["cb_off"], item["stride_c"]), (item["cr_off"], item["stride_c"]))):
+        x, y, w, h = sbt_coded_tile(W >> (c > 0), H >> (c > 0), mode)
+        o = out[c]
+        o["resi_off"], o["stride"], o["x"], o["y"], o["width"], o["height"] = int(off) + y * int(stride) + x, stride, x, y, w, h
+        if c == 0 and (h if ver else w) <= 32:
+            o["tr_hor"], o["tr_ver"] = (DCT8 if ver and not pos1 else DST7), (DCT8 if not ver and not pos1 else DST7)
+    return out
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -491,6 +541,100 @@ class HotPath:
         self.tu_rdo_multi_strided(joint, strides, jobs, bit_depth)
         self.ict_inv_batch(joint_rec, it, stats, rec, resi, sse)
         return joint, dist, rec, sse
+
+    # ---- sub-block transform (SBT) around the TU lists ----
+    def sbt_parts_batch(self, resi, items, chroma_weight=1.0, parts=None, est=None, order=None):
+        """vvhip_sbt_parts_batch: resi = int16 DEVICE tensor holding the CUs' Y / Cb / Cr residual blocks, items = SBT_ITEM_DTYPE records (HOST array); parts [n, 3, 16] and
+        est [n, 9] uint64-sized tensors (torch.int64 storage), order [n, 8] uint8 — each may be None."""
+        it = np.ascontiguousarray(items, SBT_ITEM_DTYPE)
+        self._ck(self.L.vvhip_sbt_parts_batch(self.ctx, _ptr(resi), it.ctypes.data_as(C.c_void_p) if it.size else None, int(it.size), float(chroma_weight), _ptr(parts), _ptr(est),
+                                              _ptr(order)))
+        return parts, est, order
+
+    def sbt_tiles(self, item, mode):
+        """vvhip_sbt_tiles (the library's own host arithmetic; the module function sbt_tiles mirrors it) -> SBT_TILE_DTYPE [3]"""
+        it = np.ascontiguousarray(item, SBT_ITEM_DTYPE).reshape(1)
+        out = np.zeros(3, SBT_TILE_DTYPE)
+        self._ck(self.L.vvhip_sbt_tiles(it.ctypes.data_as(C.c_void_p), int(mode), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sbt_place_batch(self, tile_rec, items, stats=None, rec=None, org_resi=None, sse=None):
+        """vvhip_sbt_place_batch: tile_rec = int16 DEVICE tensor of the compact tile reconstructions, items = SBT_PLACE_DTYPE records (HOST array), stats = the TU jobs'
+        statistics the items' stats_idx index, rec = int16 tensor laid out like the residual (every CU block is written whole) or None, org_resi + sse = the original
+        residuals and a uint64-sized tensor [n, 3] (torch.int64 storage) for the Y / Cb / Cr SSEs, or None."""
+        it = np.ascontiguousarray(items, SBT_PLACE_DTYPE)
+        self._ck(self.L.vvhip_sbt_place_batch(self.ctx, _ptr(tile_rec), it.ctypes.data_as(C.c_void_p) if it.size else None, int(it.size), _ptr(stats), _ptr(rec), _ptr(org_resi),
+                                              _ptr(sse)))
+        return rec, sse
+
+    def make_sbt_tu_jobs(self, items, candidates, qps, irap=0, thr_val=8, drop=()):
+        """the TU jobs of a list of SBT candidates: items = SBT_ITEM_DTYPE records, candidates = (CU index, SBT mode 0..7) each, qps = per candidate the QPs of (Y, Cb, Cr)
+        (or one triple for all).  One TU per component and candidate — the coded tile, read in place in the CUs' residual buffer — grouped into jobs by (width, height,
+        types, pitch) with the TUs of a job in list order; levels and reconstruction of a job are compact.  drop = (candidate, component) pairs whose coefficients the caller
+        drops (cbf 0): no TU, stats_idx -1.
+        -> (place_items, jobs, strides, level, tile_rec, stats): SBT_PLACE_DTYPE records whose tile_off / stats_idx name the TUs' outputs, a make_tu_jobs list with the
+        per-job pitches, and the three output buffers the jobs' tensors are views of."""
+        it = np.ascontiguousarray(items, SBT_ITEM_DTYPE)
+        qps = np.broadcast_to(np.asarray(qps, np.int32), (len(candidates), 3))
+        place = np.zeros(len(candidates), SBT_PLACE_DTYPE)
+        groups = {}
+        for k, (cu, mode) in enumerate(candidates):
+            for name in ("y_off", "cb_off", "cr_off", "stride_y", "stride_c", "width", "height", "sbt_allowed"):
+                place[k][name] = it[cu][name]
+            place[k]["mode"] = mode
+            place[k]["stats_idx"] = -1
+            for c, t in enumerate(sbt_tiles(it[cu], mode)):
+                if (k, c) not in drop:
+                    groups.setdefault((int(t["width"]), int(t["height"]), int(t["tr_hor"]), int(t["tr_ver"]), int(t["stride"])), []).append((k, c, int(t["resi_off"])))
+        total = sum(((w * h * len(v) + 7) & ~7) for (w, h, _, _, _), v in groups.items())      # (every job's compact outputs start 16-byte aligned)
+        n_tus = sum(len(v) for v in groups.values())
+        level, tile_rec = (torch.zeros(max(total, 1), dtype=torch.int16, device=self.device) for _ in range(2))
+        stats = torch.zeros((max(n_tus, 1), STATS_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        jobs, strides, first, base = [], [], 0, 0
+        for key in sorted(groups, reverse=True):
+            w, h, th, tv, stride = key
+            tus = groups[key]
+            for j, (k, c, _) in enumerate(tus):
+                place[k]["tile_off"][c], place[k]["stats_idx"][c] = base + j * w * h, first + j
+            qp = np.array([qps[k][c] for (k, c, _) in tus], np.int32)
+            luma = np.array([c == 0 for (_, c, _) in tus], np.int16)
+            jobs.append((w, h, th, tv, len(tus), thr_val, self.to_device(np.array([o for (_, _, o) in tus], np.int32)), self.to_device(self.tu_qp(qp, irap, luma)),
+                         level[base:base + len(tus) * w * h], tile_rec[base:base + len(tus) * w * h], stats[first:first + len(tus)]))
+            strides.append(stride)
+            first += len(tus)
+            base += (len(tus) * w * h + 7) & ~7
+        return place, jobs, strides, level, tile_rec, stats
+
+    def tu_rdo_sbt(self, resi, cus, candidates, qps, chroma_weight=1.0, bit_depth=10, irap=0, thr_val=8, drop=()):
+        """the SBT chain of a picture's inter CUs on the device: sbt_parts_batch -> tu_rdo_multi_strided on the coded tiles, read in place -> sbt_place_batch (with the jobs'
+        statistics, so it holds with sparse outputs on).  resi = int16 DEVICE tensor with the CUs' residual blocks, cus = SBT_ITEM_DTYPE records, candidates = (CU index,
+        mode) each, qps as make_sbt_tu_jobs takes them.  Candidates of one CU share its block of the reconstruction, so the r-th candidate of every CU is placed into plane r
+        of rec, one placement call per plane.
+        -> (parts [n, 3, 16], est [n, 9], order [n, 8], rec [planes, resi.numel()], sse [candidates, 3], levels, stats): levels / stats as make_sbt_tu_jobs lays them out
+        (the returned place items of hp.last_sbt_place name them)."""
+        it = np.ascontiguousarray(cus, SBT_ITEM_DTYPE)
+        n = int(it.size)
+        parts = torch.empty((n, 3, 16), dtype=torch.int64, device=self.device)
+        est = torch.empty((n, 9), dtype=torch.int64, device=self.device)
+        order = torch.empty((n, 8), dtype=torch.uint8, device=self.device)
+        self.sbt_parts_batch(resi, it, chroma_weight, parts, est, order)
+        place, jobs, strides, level, tile_rec, stats = self.make_sbt_tu_jobs(it, candidates, qps, irap, thr_val, drop)
+        self.last_sbt_place = place
+        if jobs:
+            self.tu_rdo_multi_strided(resi, strides, jobs, bit_depth)
+        seen, plane_of = {}, []
+        for (cu, _) in candidates:
+            plane_of.append(seen.get(cu, 0))
+            seen[cu] = plane_of[-1] + 1
+        planes = max(plane_of, default=-1) + 1
+        rec = torch.zeros((max(planes, 1), resi.numel()), dtype=torch.int16, device=self.device)
+        sse = torch.zeros((len(candidates), 3), dtype=torch.int64, device=self.device)
+        for r in range(planes):
+            ks = [k for k in range(len(candidates)) if plane_of[k] == r]
+            part = torch.empty((len(ks), 3), dtype=torch.int64, device=self.device)
+            self.sbt_place_batch(tile_rec, place[ks], stats, rec[r], resi, part)
+            sse[torch.as_tensor(ks, device=self.device)] = part
+        return parts, est, order, rec, sse, level, stats
 
     # ---- motion-search plans: integer candidates + sub-pel stages + plain table calls of a picture in one launch ----
     def me_plan_create(self, int_jobs, cands, stage_jobs, items, bit_depth=10, max_window=0, mask_items=None):
