@@ -847,7 +847,12 @@ VVHIP_API int vvhip_mctf_filter_params( int qp, int bit_depth, double overall_st
  *   result              : mvd = cu.mvdL0SubPu[num] in 1/16 sample (list 1 moves by -mvd), min_cost = the value the BDOF switch compares
  *                         with 2*dx*dy (:1386).  The final motion compensation: sub-blocks whose refinement is zero go into a prediction list
  *                         (vvhip_pred_inter_batch: luma + chroma, both lists, the average); a refined sub-block reads through DMVR's padded-reference
- *                         rule (xFinalPaddedMCForDMVR, :1189-1225), with BDOF where min_cost allows it: vvhip_pred_inter_batch_ex.            */
+ *                         rule (xFinalPaddedMCForDMVR, :1189-1225), with BDOF where min_cost allows it: vvhip_pred_inter_batch_ex.
+ *   read footprint      : of either list, relative to the sample at ref*_off and whatever the fractions are: rows -2 .. dy + 2 and columns -2 .. 8 * segs - 1 with
+ *                         segs = (dx + 4 + 7) >> 3 — 13 (dy 8) or 21 (dy 16) rows of 18 (dx 8) or 26 (dx 16) samples.  The reference reads rows -2 .. dy + 1 and columns
+ *                         -2 .. dx + 1, and one more row / column where the vertical / horizontal fraction is not 0; the kernel loads whole lanes of ten samples at a pitch
+ *                         of eight and always the extra row, so up to six more columns to the right and one more row below.  These samples must lie inside the
+ *                         allocation (they may belong to the next row of the plane); their values never reach a result.                                  */
 typedef struct { int32_t ref0_off, ref1_off; int16_t frac0_x, frac0_y, frac1_x, frac1_y; } vvhip_dmvr_item;
 typedef struct { int16_t mvd_x, mvd_y; int32_t pad; uint64_t min_cost; } vvhip_dmvr_result;
 VVHIP_API int vvhip_dmvr_refine_batch( vvhip_ctx* ctx, const int16_t* d_ref0, int stride0, const int16_t* d_ref1, int stride1,

@@ -841,7 +841,9 @@ bool DMVROps::refineCu( const Pel* ref0, int stride0, int fx0, int fy0, const Pe
 {
   if( ( dx != 8 && dx != 16 ) || ( dy != 8 && dy != 16 ) || cuWidth % dx || cuHeight % dy || bitDepth > 10 ) return false;
   Device& dev = Device::get();
-  // the bilinear prediction of the (w+4) x (h+4) area reads one more column / row: stage (w+5) x (h+5) of each list, compact
+  // the bilinear prediction of the (w+4) x (h+4) area reads one more column / row: stage (w+5) x (h+5) of each list, compact.  The device entry loads whole lanes (its
+  // footprint in vvenc_hip.h: columns up to 8 * segs - 1 = dx + 7 right of a sub-block): the last sub-block column runs five samples past a row of this window — into the
+  // next row, from list 0's last row into list 1, and from list 1's last row into the slack of the staging request below (256 bytes for these 10)
   const int pw = cuWidth + 5, ph = cuHeight + 5;
   std::vector<Pel> host( ( size_t ) 2 * pw * ph );
   for( int y = 0; y < ph; y++ )

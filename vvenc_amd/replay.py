@@ -250,6 +250,7 @@ class RecordedLists:
         # ---- DMVR: one list per (reference 0, reference 1, sub-block size)
         self.dmvr_groups = []
         dm = pic.dmvr
+        n_dmvr_dropped = 0
         if dm.size:
             key = np.stack([dm["ref0Plane"], dm["ref1Plane"], dm["dx"], dm["dy"]], 1).astype(np.int64)
             uniq, inv = np.unique(key, axis=0, return_inverse=True)
@@ -262,7 +263,20 @@ class RecordedLists:
                 it["ref1_off"] = (dm["y1"][sel_d].astype(np.int64) + 2) * strides[r1] + dm["x1"][sel_d] + 2
                 for f in ("frac0_x", "frac0_y", "frac1_x", "frac1_y"):
                     it[f] = dm[f.replace("_", "")][sel_d]
+                # the entry point loads more than the reference reads (vvenc_hip.h: rows -2 .. dy + 2 and columns -2 .. 8 * segs - 1 around ref*_off, whatever the fractions): up to
+                # six samples and one row past the search area.  A plane's row of slack covers a search area that ends on the last row of the margin unless it also ends in the
+                # last columns; a sub-block whose loads would leave a plane's storage stays out of the list and is counted
+                segs = (int(dx) + 4 + 7) >> 3
+                keep = np.ones(sel_d.size, bool)
+                for r, off in ((r0, it["ref0_off"]), (r1, it["ref1_off"])):
+                    first = self.planes[r].origin + off.astype(np.int64) - 2 * strides[r] - 2
+                    keep &= (first >= 0) & (first + (int(dy) + 4) * strides[r] + 8 * segs + 1 < self.planes[r].storage.size)
+                n_dmvr_dropped += int((~keep).sum())
+                sel_d, it = sel_d[keep], it[keep]
+                if not sel_d.size:
+                    continue
                 self.dmvr_groups.append(dict(r0=int(r0), r1=int(r1), dx=int(dx), dy=int(dy), n=int(sel_d.size), index=sel_d, items=it))
+        self.dropped["dmvr_subblocks"] = n_dmvr_dropped
         self.nothing_dropped = not any(self.dropped.values())
 
         # ---- accounting (SURVEY 8d figures per unit)
