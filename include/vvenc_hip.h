@@ -909,6 +909,75 @@ VVHIP_API int vvhip_alf_filter_plane( vvhip_ctx* ctx, const int16_t* d_src, ptrd
 VVHIP_API int vvhip_ccalf_filter_plane( vvhip_ctx* ctx, int16_t* d_dst_c, ptrdiff_t dst_stride, const int16_t* d_rec_luma, ptrdiff_t rec_stride, int width_c, int height_c, int ctu_size_c,
                                         int shift_x, int shift_y, int bit_depth, const int16_t* d_coeff, const uint8_t* d_ctu_filter, int vb_ctu_height, int vb_pos );
 
+/* ======================================================================================================================
+ * SAO (sample adaptive offset), the stage in front of ALF in the per-CTU pipeline CTU_ENCODE -> LF -> SAO -> ALF (EncoderLib/EncSlice.cpp:1058-1141): the statistics of a
+ * picture and the offset filtering of a picture, each ONE launch for up to 3 planes and a band of CTU rows.  With both, a deblocked picture is uploaded once and stays in
+ * HBM through to the ALF entries above.
+ *   vvhip_sao_stats  <- EncSampleAdaptiveOffset::getBlkStats (EncoderLib/EncSampleAdaptiveOffset.cpp:810-929) + the five calcSaoStatistics*_Core routines
+ *       (CommonLib/SampleAdaptiveOffset.cpp:281-399) for every CTU, as getStatistics (:294-344) and getCtuStatistics (:239-292) drive them.
+ *       d_out: int64 [ctu][plane][5][2][32] at the CTU's PICTURE-WIDE raster index — byte-compatible with SAOStatData[5] per CTU and plane ({ int64 diff[32]; int64 count[32]; },
+ *       order EO_0, EO_90, EO_135, EO_45, BO; edge classes at 0..4 = edgeType + 2, bands at src >> ( bit_depth - 5 )).  Every record of the band is written completely
+ *       (zeros and the unused indices 5..31 of the edge types included: no pre-zeroing), nothing else is written.  Integer sums: bit-identical in any order and from run to run.
+ *       flags_host (may be NULL): one byte per CTU of the PICTURE (raster; only the band's entries are read), VVHIP_SAO_* bits = isLeftAvail, isAboveAvail, isAboveLeftAvail
+ *       (slice / tile structure: the caller's deriveLoopFilterBoundaryAvailibility) and isRightAvail, isBelowAvail, isAboveRightAvail.  NULL: the picture's borders alone
+ *       decide, as in getStatistics.  Where the right / below CTU is available the right 5 columns / bottom 4 rows of a luma CTU (3 / 2 of a chroma CTU: is_luma) are left
+ *       out — they are not deblocked yet when the CTU's statistics are taken in the pipeline.
+ *   vvhip_sao_offset <- offsetBlock_core (CommonLib/SampleAdaptiveOffset.cpp:64-280) as offsetCTU drives it (:605-652) from the DECIDED parameters of every CTU and plane:
+ *       params_host [ctu][plane] at the picture-wide raster index (only the band's are read).  type -1 = SAO_MODE_OFF, 0..3 = EO_0, EO_90, EO_135, EO_45 with offs[edgeType + 2]
+ *       (all five as given), 4 = BO with offs[i] on band ( band + i ) & 31, i < 4 — everything reconstructBlkSAOParam can produce, and the subset on which the reference's
+ *       scalar and x86 rows agree.  avail = the reference's 8-bit mask (SampleAdaptiveOffset.h:75-85: 1 left, 2 right, 4 above, 8 below, 16 above-left, 32 above-right,
+ *       64 below-left, 128 below-right).  d_dst receives the complete plane rows of the band: the filtered samples (clipped to [clip_min, clip_max], also where the offset is 0),
+ *       and the source value everywhere else — outside the processed ranges and in CTUs that are off.  d_src is never written and must not overlap any d_dst.
+ * Planes: any strides (in samples, >= width) and any base alignment; samples are read only inside width x height, no border is needed.  ctu_w / ctu_h are in the plane's
+ * own samples (8..128); all planes of a call must have the same CTU grid.  Band = CTU rows [ctu_row0, ctu_row0 + n_rows), n_rows >= 1.
+ * Operand contract: 0 <= src < 2^bit_depth (the band index is src >> ( bit_depth - 5 ); a violation lands in band ( index & 31 )), bit_depth 8..12, | org - src | < 2^15.
+ * VVHIP_E_ARG: no planes / more than 3; a CTU size outside 8..128; planes with different CTU grids; a last CTU column or row of ONE sample (the reference's diagonal types read
+ * past their block there); a band outside the picture; a flag / availability bit set for a neighbour outside the picture; a type outside -1..4, band > 31, rsv != 0;
+ * clip_min > clip_max; a source plane that overlaps a destination plane (compared as spans, first to last sample: rows of two planes interleaved in one buffer overlap).
+ * The filter follows offsetBlock_core for EVERY mask.  The reference's x86 row equals it on the masks a picture's borders give, and in general unless left, right, above-left
+ * and below-right are all set while above or below is not (EO_135, EO_45) or above-right or below-left is not (EO_45); it also clips to the bit depth whatever the ClpRng.
+ * Still the caller's: decideCtuParams / deriveOffsets / the rate estimation (serial over CTUs: CABAC contexts and the left / above merge candidates; they read only the
+ * 2560-byte records), the merge list, decidePicParams, and the per-CTU pipeline timing of storeCtuReco.                                                                        */
+#define VVHIP_SAO_LEFT        1
+#define VVHIP_SAO_ABOVE       2
+#define VVHIP_SAO_ABOVE_LEFT  4
+#define VVHIP_SAO_RIGHT       8
+#define VVHIP_SAO_BELOW       16
+#define VVHIP_SAO_ABOVE_RIGHT 32
+#define VVHIP_SAO_REC         320   /* int64 per CTU and plane: [5][2][32] */
+typedef struct
+{
+  const int16_t* d_org;            /* the original plane                                                          */
+  const int16_t* d_src;            /* the deblocked plane                                                         */
+  int32_t org_stride, src_stride;  /* in samples                                                                  */
+  int32_t width, height;           /* of the plane                                                                */
+  int32_t ctu_w, ctu_h;            /* CTU size in the plane's own samples, 8..128                                 */
+  int32_t bit_depth;               /* 8..12                                                                       */
+  int32_t is_luma;                 /* skipped columns / rows: 5 / 4 (luma) or 3 / 2 (chroma)                      */
+} vvhip_sao_stats_plane;           /* 48 bytes */
+typedef struct
+{
+  const int16_t* d_src;            /* the deblocked plane, never written                                          */
+  int16_t* d_dst;                  /* the SAO'd plane                                                             */
+  int32_t src_stride, dst_stride;
+  int32_t width, height;
+  int32_t ctu_w, ctu_h;
+  int32_t bit_depth;
+  int32_t clip_min, clip_max;      /* ClpRng of the component                                                     */
+  int32_t rsv;
+} vvhip_sao_offset_plane;          /* 56 bytes */
+typedef struct
+{
+  int8_t  type;                    /* -1 off, 0..3 EO_0 / EO_90 / EO_135 / EO_45, 4 BO                            */
+  uint8_t avail;                   /* the reference's availability mask of the CTU                                */
+  uint8_t band;                    /* BO: first band (typeAuxInfo), 0..31                                         */
+  uint8_t rsv;                     /* 0                                                                           */
+  int16_t offs[5];                 /* EO: offs[edgeType + 2]; BO: offs[0..3]                                      */
+} vvhip_sao_param;                 /* 14 bytes */
+VVHIP_API int vvhip_sao_stats( vvhip_ctx* ctx, const vvhip_sao_stats_plane* planes, int n_planes, int ctu_row0, int n_rows, const uint8_t* flags_host /* may be NULL */,
+                               int64_t* d_out );
+VVHIP_API int vvhip_sao_offset( vvhip_ctx* ctx, const vvhip_sao_offset_plane* planes, int n_planes, const vvhip_sao_param* params_host, int ctu_row0, int n_rows );
+
 #ifdef __cplusplus
 }
 #endif

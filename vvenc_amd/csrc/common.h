@@ -82,6 +82,16 @@ struct vvhip_ctx
   // the same for the sub-block transform entries (sbt.hip): [0] vvhip_sbt_parts_batch, [1] vvhip_sbt_place_batch — slots of their own again, so that alternating them with the
   // joint Cb-Cr and the prediction entries on one context evicts none of theirs
   IctSched sbtSched[2];
+  // the per-call host arrays of the SAO entries (sao.hip): [0] the CTU flags of vvhip_sao_stats, [1] the CTU parameters of vvhip_sao_offset — device slot, the host copy the
+  // asynchronous upload reads, and the event recorded behind the launch that reads the slot
+  struct SaoSlot
+  {
+    void*        d         = nullptr;
+    size_t       bytes     = 0;
+    std::vector<unsigned char> blob;
+    hipEvent_t   event     = nullptr;
+    bool         eventRecorded = false;
+  } saoSlot[2];
   // how the host waits for the stream (vvhip_set_blocking_sync): false = hipStreamSynchronize (the runtime's low-latency wait), true = a blocking event — the calling thread
   // sleeps, which matters when the host's cores are all busy encoding
   bool         blockingSync = false;

@@ -265,6 +265,11 @@ void vvhip_destroy( vvhip_ctx* ctx )
     if( S.d_sched ) ( void ) hipFree( S.d_sched );
     if( S.event ) ( void ) hipEventDestroy( S.event );
   }
+  for( vvhip_ctx::SaoSlot& S : ctx->saoSlot )
+  {
+    if( S.d ) ( void ) hipFree( S.d );
+    if( S.event ) ( void ) hipEventDestroy( S.event );
+  }
   if( ctx->d_affSched ) ( void ) hipFree( ctx->d_affSched );
   if( ctx->affEvent ) ( void ) hipEventDestroy( ctx->affEvent );
   if( ctx->d_mctfStats ) ( void ) hipFree( ctx->d_mctfStats );

@@ -1457,6 +1457,119 @@ bool ALFOps::statisticsEnd( const Pel* const rec[3], const uint8_t** cls, const 
 
 ALFOps::~ALFOps() {}      // (device areas are released with the process: HIP teardown order at exit is not ours to rely on)
 
+// ------------------------------------------------------------------------------------------------ SaoOps
+bool SaoOps::statisticsBegin( const int recStride[3], const int orgStride[3], int width, int height, int bitDepth, int ctuSize )
+{
+  m_open = false; m_planesResident = false;
+  if( width < 2 || height < 2 || ( width & 1 ) || ( height & 1 ) || ctuSize < 16 || ctuSize > 128 || ( ctuSize & 1 ) ) return false;
+  for( int c = 0; c < 3; c++ ) if( recStride[c] < ( c ? width >> 1 : width ) || orgStride[c] < ( c ? width >> 1 : width ) ) return false;
+  Device& dev = Device::get();
+  size_t recTotal = 0, orgTotal = 0;
+  for( int c = 0; c < 3; c++ )
+  {
+    const int h = c ? height >> 1 : height;
+    m_rp[c] = recStride[c]; m_op[c] = orgStride[c];
+    m_off[c] = recTotal;  recTotal += ( ( size_t ) m_rp[c] * h + 127 ) & ~( size_t ) 127;
+    m_oOff[c] = orgTotal; orgTotal += ( ( size_t ) m_op[c] * h + 127 ) & ~( size_t ) 127;
+  }
+  const bool moved = m_gpu != dev.gpu();
+  auto grow = [&]( int16_t*& d, size_t& have, size_t want, const char* what )
+  {
+    if( !moved && have >= want ) return;
+    if( d ) vvhip_free( dev.ctx(), d );
+    void* p = nullptr;
+    d = nullptr; have = 0;
+    dev.check( vvhip_malloc( dev.ctx(), &p, want * sizeof( Pel ) + 256 ), what );
+    d = static_cast<int16_t*>( p ); have = want;
+  };
+  grow( m_dRec, m_recElems, recTotal, "SAO deblocked planes" );
+  grow( m_dOrg, m_orgElems, orgTotal, "SAO original planes" );
+  grow( m_dDst, m_dstElems, recTotal, "SAO filtered planes" );
+  const int ctusX = ( width + ctuSize - 1 ) / ctuSize, rows = ( height + ctuSize - 1 ) / ctuSize;
+  const size_t stBytes = ( size_t ) ctusX * rows * 3 * VVHIP_SAO_REC * sizeof( int64_t );
+  if( moved || m_stBytes < stBytes )
+  {
+    if( m_dSt ) vvhip_free( dev.ctx(), m_dSt );
+    void* p = nullptr;
+    m_dSt = nullptr; m_stBytes = 0;
+    dev.check( vvhip_malloc( dev.ctx(), &p, stBytes + 256 ), "SAO statistics records" );
+    m_dSt = static_cast<char*>( p ); m_stBytes = stBytes;
+  }
+  if( m_hostBytes < stBytes )
+  {
+    if( m_host ) vvhip_host_free( dev.ctx(), m_host );
+    void* p = nullptr;
+    m_host = nullptr; m_hostBytes = 0;
+    dev.check( vvhip_host_alloc( dev.ctx(), &p, stBytes + 64 ), "SAO statistics download area" );
+    m_host = static_cast<char*>( p ); m_hostBytes = stBytes;
+  }
+  while( ( int ) m_events.size() < rows ) { void* e = nullptr; dev.check( vvhip_event_create( dev.ctx(), &e ), "SAO band mark" ); m_events.push_back( e ); }
+  m_done.assign( ( size_t ) rows, 0 );
+  m_gpu = dev.gpu(); m_rows = rows; m_issued = 0; m_width = width; m_height = height; m_bitDepth = bitDepth; m_ctuSize = ctuSize; m_ctusX = ctusX;
+  m_open = true;
+  return true;
+}
+
+bool SaoOps::statisticsBand( int ctuRow, const Pel* const rec[3], const Pel* const org[3] )
+{
+  Device& dev = Device::get();
+  if( !m_open || ctuRow < 0 || ctuRow >= m_rows || m_done[ctuRow] || dev.gpu() != m_gpu ) return false;
+  vvhip_sao_stats_plane pl[3];
+  for( int c = 0; c < 3; c++ )
+  {
+    const int w = c ? m_width >> 1 : m_width, h = c ? m_height >> 1 : m_height, cs = c ? m_ctuSize >> 1 : m_ctuSize;
+    const int y0 = ctuRow * cs, bh = std::min( cs, h - y0 ), ya = std::max( 0, y0 - 1 ), yb = std::min( h, y0 + bh + 1 );
+    // the band's rows and one row above and below: everything its statistics read (the rows two bands share arrive twice with the same values)
+    dev.check( vvhip_upload( dev.ctx(), m_dRec + m_off[c] + ( size_t ) ya * m_rp[c], rec[c] + ( ptrdiff_t ) ya * m_rp[c], ( ( size_t ) m_rp[c] * ( yb - ya - 1 ) + w ) * sizeof( Pel ) ), "SAO rec band" );
+    dev.check( vvhip_upload( dev.ctx(), m_dOrg + m_oOff[c] + ( size_t ) y0 * m_op[c], org[c] + ( ptrdiff_t ) y0 * m_op[c], ( ( size_t ) m_op[c] * ( bh - 1 ) + w ) * sizeof( Pel ) ), "SAO org band" );
+    pl[c].d_org = m_dOrg + m_oOff[c]; pl[c].d_src = m_dRec + m_off[c]; pl[c].org_stride = m_op[c]; pl[c].src_stride = m_rp[c]; pl[c].width = w; pl[c].height = h;
+    pl[c].ctu_w = cs; pl[c].ctu_h = cs; pl[c].bit_depth = m_bitDepth; pl[c].is_luma = c == 0;
+    if( m_issued == 0 ) m_rec[c] = rec[c]; else if( m_rec[c] != rec[c] ) m_rec[c] = nullptr;
+  }
+  int64_t* dSt = reinterpret_cast<int64_t*>( m_dSt );
+  dev.check( vvhip_sao_stats( dev.ctx(), pl, 3, ctuRow, 1, nullptr, dSt ), "vvhip_sao_stats (band)" );
+  const size_t bytes = ( size_t ) m_ctusX * 3 * VVHIP_SAO_REC * sizeof( int64_t );
+  dev.check( vvhip_download_async( dev.ctx(), m_host + ( size_t ) ctuRow * bytes, m_dSt + ( size_t ) ctuRow * bytes, bytes ), "SAO statistics band" );
+  dev.check( vvhip_event_record( dev.ctx(), m_events[ctuRow] ), "SAO band mark" );
+  m_done[ctuRow] = 1; m_issued++;
+  return true;
+}
+
+bool SaoOps::statisticsEnd( const int64_t** out )
+{
+  if( !m_open || m_issued != m_rows ) return false;
+  Device& dev = Device::get();
+  for( int r = 0; r < m_rows; r++ ) dev.check( vvhip_event_wait( dev.ctx(), m_events[r] ), "SAO band mark" );
+  *out = reinterpret_cast<const int64_t*>( m_host );
+  m_planesResident = m_rec[0] && m_rec[1] && m_rec[2];      // every row of the deblocked planes is in HBM now
+  return true;
+}
+
+bool SaoOps::offsetPicture( const Pel* const src[3], const vvhip_sao_param* params, Pel* const dst[3], const int dstStride[3] )
+{
+  Device& dev = Device::get();
+  if( !m_open || dev.gpu() != m_gpu || !params ) return false;
+  const bool res = m_planesResident && m_issued == m_rows && src[0] == m_rec[0] && src[1] == m_rec[1] && src[2] == m_rec[2];
+  vvhip_sao_offset_plane pl[3];
+  for( int c = 0; c < 3; c++ )
+  {
+    const int w = c ? m_width >> 1 : m_width, h = c ? m_height >> 1 : m_height, cs = c ? m_ctuSize >> 1 : m_ctuSize;
+    if( dstStride[c] < w ) return false;
+    if( !res ) dev.check( vvhip_upload( dev.ctx(), m_dRec + m_off[c], src[c], ( ( size_t ) m_rp[c] * ( h - 1 ) + w ) * sizeof( Pel ) ), "SAO source plane" );
+    pl[c].d_src = m_dRec + m_off[c]; pl[c].d_dst = m_dDst + m_off[c]; pl[c].src_stride = m_rp[c]; pl[c].dst_stride = m_rp[c]; pl[c].width = w; pl[c].height = h;
+    pl[c].ctu_w = cs; pl[c].ctu_h = cs; pl[c].bit_depth = m_bitDepth; pl[c].clip_min = 0; pl[c].clip_max = ( 1 << m_bitDepth ) - 1; pl[c].rsv = 0;
+  }
+  dev.check( vvhip_sao_offset( dev.ctx(), pl, 3, params, 0, m_rows ), "vvhip_sao_offset" );
+  for( int c = 0; c < 3; c++ )
+  {
+    const int w = c ? m_width >> 1 : m_width, h = c ? m_height >> 1 : m_height;
+    dev.check( vvhip_download_2d( dev.ctx(), dst[c], ( size_t ) dstStride[c] * sizeof( Pel ), m_dDst + m_off[c], ( size_t ) m_rp[c] * sizeof( Pel ), ( size_t ) w * sizeof( Pel ), ( size_t ) h ), "SAO filtered plane" );
+  }
+  return true;
+}
+
+SaoOps::~SaoOps() {}      // (device areas are released with the process, like ALFOps')
+
 bool ALFOps::getStatisticsCcAlf( const Pel* orgC, int orgStride, const Pel* slfC, int slfStride, const Pel* recLuma, int recStride, int widthC, int heightC, int ctuSizeC,
                                  int vbCTUHeight, int vbPos, int picHeight, float* out, const float* init )
 {

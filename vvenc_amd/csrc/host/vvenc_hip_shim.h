@@ -372,6 +372,38 @@ private:
                         int filterLength, const uint8_t* cls, const short* coeffSets, const short* clipSets, int numSets, const short* ctuSet, int vbCTUHeight, int vbPos );
 };
 
+// SAO of a picture (vvhip_sao_stats / vvhip_sao_offset), 4:2:0: the statistics of EncSampleAdaptiveOffset::getCtuStatistics / getBlkStats
+// (EncoderLib/EncSampleAdaptiveOffset.cpp:239-292, :810-929) for whole CTU rows, and SampleAdaptiveOffset::offsetCTU (CommonLib/SampleAdaptiveOffset.cpp:605-652) for the
+// whole picture.  Availability: the picture's borders (filtering across slices and tiles on, one slice: what getStatistics assumes).  decideCtuParams — serial over CTUs,
+// CABAC contexts and merge candidates — stays with the encoder: it reads the records statisticsEnd hands out and produces the parameters offsetPicture takes.
+struct SaoOps
+{
+  // statisticsBegin sets the picture up (any thread): line pitches of the deblocked ("rec") and the original planes, luma size, bit depth, luma CTU size (8..128).
+  // statisticsBand( r ) uploads CTU row r of the three planes plus one row above and below it from the encoder's planes, runs the statistics of that row's CTUs and requests
+  // their download into pinned host memory — all asynchronous on the CALLING thread's stream, completion marked by an event.  In the encoder's pipeline a row's task may run
+  // once the row below it is deblocked (the rows it reads are final then; the columns and rows a CTU leaves out are those that are not).  statisticsEnd waits for the marks:
+  // out = int64 [ctus][3][5][2][32], byte-compatible with SAOStatData[5] per CTU and component; false: not every band was issued.
+  // The caller serialises the calls per object; bands may come in any order, each exactly once.
+  bool statisticsBegin( const int recStride[3], const int orgStride[3], int width, int height, int bitDepth, int ctuSize );
+  int  statisticsBands() const { return m_rows; }
+  bool statisticsBand( int ctuRow, const Pel* const rec[3], const Pel* const org[3] );
+  bool statisticsEnd( const int64_t** out );
+  // offsetCTU over the picture begun last: params [ctus][3] (vvhip_sao_param: type -1 = off), clip range [0, 2^bitDepth - 1].  src handed over with the planes the bands
+  // uploaded (same pointers, every band issued) is not uploaded again.  dst[c] (line pitch dstStride[c]) receives the whole SAO'd plane; the copy stays in HBM
+  // (residentPlane) for the ALF entries.  false: no picture begun, or one on another GPU.
+  bool offsetPicture( const Pel* const src[3], const vvhip_sao_param* params, Pel* const dst[3], const int dstStride[3] );
+  const int16_t* residentPlane( int c ) const { return m_dDst ? m_dDst + m_off[c] : nullptr; }      // device pointer, line pitch = recStride[c]
+  ~SaoOps();
+private:
+  bool m_open = false, m_planesResident = false;
+  int m_gpu = -1, m_rows = 0, m_issued = 0, m_width = 0, m_height = 0, m_bitDepth = 0, m_ctuSize = 0, m_ctusX = 0;
+  int m_rp[3] = { 0, 0, 0 }, m_op[3] = { 0, 0, 0 };
+  size_t m_off[3] = { 0, 0, 0 }, m_oOff[3] = { 0, 0, 0 }, m_recElems = 0, m_orgElems = 0, m_stBytes = 0, m_hostBytes = 0, m_dstElems = 0;
+  const Pel* m_rec[3] = { nullptr, nullptr, nullptr };
+  int16_t* m_dRec = nullptr; int16_t* m_dOrg = nullptr; int16_t* m_dDst = nullptr; char* m_dSt = nullptr; char* m_host = nullptr;
+  std::vector<void*> m_events; std::vector<char> m_done;
+};
+
 // MCTF table, CommonLib/MCTF.h:160-170
 struct MCTFOps
 {

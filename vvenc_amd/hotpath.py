@@ -100,6 +100,12 @@ SBT_TILE_DTYPE = np.dtype([("resi_off", "<i4"), ("stride", "<i4"), ("x", "<i2"),
 SBT_PLACE_DTYPE = np.dtype([("y_off", "<i4"), ("cb_off", "<i4"), ("cr_off", "<i4"), ("stride_y", "<i4"), ("stride_c", "<i4"), ("tile_off", "<i4", (3,)), ("stats_idx", "<i4", (3,)),
                             ("width", "<i2"), ("height", "<i2"), ("sbt_allowed", "u1"), ("mode", "u1"), ("rsv", "u1", (2,))])      # vvhip_sbt_place_item (52 bytes)
 SBT_VER_HALF, SBT_HOR_HALF, SBT_VER_QUAD, SBT_HOR_QUAD = 1, 2, 3, 4      # SbtIdx (TypeDef.h:266-270): the bits of sbt_allowed; SBT mode = 2 * ( idx - 1 ) + pos
+SAO_PARAM_DTYPE = np.dtype([("type", "i1"), ("avail", "u1"), ("band", "u1"), ("rsv", "u1"), ("offs", "<i2", (5,))])      # vvhip_sao_param (14 bytes)
+SAO_OFF, SAO_EO_0, SAO_EO_90, SAO_EO_135, SAO_EO_45, SAO_BO = -1, 0, 1, 2, 3, 4
+SAO_LEFT, SAO_ABOVE, SAO_ABOVE_LEFT, SAO_RIGHT, SAO_BELOW, SAO_ABOVE_RIGHT = 1, 2, 4, 8, 16, 32      # VVHIP_SAO_*: the statistics flags of a CTU
+# the reference's availability mask of the filter (SampleAdaptiveOffset.h:75-85)
+SAO_AVAIL_LEFT, SAO_AVAIL_RIGHT, SAO_AVAIL_ABOVE, SAO_AVAIL_BELOW, SAO_AVAIL_ABOVE_LEFT, SAO_AVAIL_ABOVE_RIGHT, SAO_AVAIL_BELOW_LEFT, SAO_AVAIL_BELOW_RIGHT = 1, 2, 4, 8, 16, 32, 64, 128
+SAO_REC = 320      # VVHIP_SAO_REC: int64 per CTU and plane, [5][2][32] = SAOStatData[5]
 SBT_MAX_DIST = (1 << 64) - 1      # MAX_DISTORTION: the estimate of a mode whose type is not allowed
 
 
@@ -182,6 +188,22 @@ class Plane:
 
     def visible(self):
         return self.storage[self.pad:self.pad + self.height, self.pad:self.pad + self.width]
+
+
+class PlaneView:
+    """width x height samples at element `offset` of a device int16 tensor, line pitch `stride`: a plane at any base alignment and pitch (what the SAO entries accept)"""
+
+    def __init__(self, storage, offset, stride, width, height):
+        assert storage.is_cuda and storage.dtype == torch.int16 and storage.is_contiguous()
+        assert offset >= 0 and offset + (height - 1) * stride + width <= storage.numel()
+        self.storage, self.off, self.stride, self.width, self.height = storage, int(offset), int(stride), int(width), int(height)
+
+    @property
+    def buf_ptr(self):
+        return C.c_void_p(self.storage.data_ptr() + 2 * self.off)
+
+    def visible(self):
+        return torch.as_strided(self.storage.view(-1), (self.height, self.width), (self.stride, 1), self.off)
 
 
 class HotPath:
@@ -726,6 +748,53 @@ class HotPath:
         self._ck(self.L.vvhip_ccalf_filter_plane(self.ctx, dst_c.buf_ptr, dst_c.stride, rec_luma.buf_ptr, rec_luma.stride, dst_c.width, dst_c.height, ctu_size_c, shift[0], shift[1], bit_depth,
                                                  _ptr(d_coeff), _ptr(d_ctu_filter), vb_ctu_height, vb_pos))
         return dst_c
+
+    # ---- SAO: statistics and offset filtering of a picture (sao.hip) ----
+    class _SaoStatsPlane(C.Structure):
+        _fields_ = [("d_org", C.c_void_p), ("d_src", C.c_void_p), ("org_stride", C.c_int32), ("src_stride", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                    ("ctu_w", C.c_int32), ("ctu_h", C.c_int32), ("bit_depth", C.c_int32), ("is_luma", C.c_int32)]
+
+    class _SaoOffsetPlane(C.Structure):
+        _fields_ = [("d_src", C.c_void_p), ("d_dst", C.c_void_p), ("src_stride", C.c_int32), ("dst_stride", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                    ("ctu_w", C.c_int32), ("ctu_h", C.c_int32), ("bit_depth", C.c_int32), ("clip_min", C.c_int32), ("clip_max", C.c_int32), ("rsv", C.c_int32)]
+
+    @staticmethod
+    def sao_geometry(planes, ctu):
+        """planes: per plane a pair of Plane / PlaneView, plane 0 first; ctu: the CTU size of plane 0, or per plane ( ctu_w, ctu_h ) -> per plane ( ctu_w, ctu_h ) and the
+        CTU grid of plane 0 ( a subsampled plane — smaller than plane 0 in a direction — has half the CTU size there: 4:2:0 / 4:2:2 )"""
+        p0 = planes[0][0]
+        if isinstance(ctu, int):
+            ctu = [(ctu if p[0].width == p0.width else ctu // 2, ctu if p[0].height == p0.height else ctu // 2) for p in planes]
+        return ctu, (-(-p0.width // ctu[0][0]), -(-p0.height // ctu[0][1]))
+
+    def sao_stats(self, planes, ctu, bit_depth, rows=None, flags=None, out=None):
+        """getBlkStats of every CTU of CTU rows `rows` = ( first, count ) (None: the picture) in one launch.  planes: per plane ( org, src ), Plane or PlaneView, plane 0 = luma.
+        flags: uint8 per CTU of the picture (SAO_* bits) or None = picture borders alone.  -> int64 tensor ( ctus of the picture, planes, 5, 2, 32 ); only the band is written"""
+        ctu, (gx, gy) = self.sao_geometry(planes, ctu)
+        rows = (0, gy) if rows is None else rows
+        if out is None:
+            out = torch.zeros((gx * gy, len(planes), 5, 2, 32), dtype=torch.int64, device=self.device)
+        desc = (self._SaoStatsPlane * len(planes))(*[self._SaoStatsPlane(o.buf_ptr, s.buf_ptr, o.stride, s.stride, s.width, s.height, cw, ch, bit_depth, int(k == 0))
+                                                     for k, ((o, s), (cw, ch)) in enumerate(zip(planes, ctu))])
+        fl = None
+        if flags is not None:
+            fl = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+            assert fl.size == gx * gy, "one flag byte per CTU of the picture"
+        self._ck(self.L.vvhip_sao_stats(self.ctx, desc, len(planes), rows[0], rows[1], fl.ctypes.data_as(C.c_void_p) if fl is not None else None, _ptr(out)))
+        return out
+
+    def sao_offset(self, planes, params, ctu, bit_depth, rows=None, clip=None):
+        """offsetBlock of every CTU of CTU rows `rows` in one launch.  planes: per plane ( src, dst ); params: SAO_PARAM_DTYPE ( ctus of the picture, planes ); clip: per plane
+        ( min, max ), None = ( 0, 2^bit_depth - 1 ).  dst receives the band's complete rows (filtered samples, the source value everywhere else)"""
+        ctu, (gx, gy) = self.sao_geometry(planes, ctu)
+        rows = (0, gy) if rows is None else rows
+        clip = [(0, (1 << bit_depth) - 1)] * len(planes) if clip is None else clip
+        prm = np.ascontiguousarray(params, SAO_PARAM_DTYPE).reshape(-1)
+        assert prm.size == gx * gy * len(planes), "one parameter record per CTU of the picture and plane"
+        desc = (self._SaoOffsetPlane * len(planes))(*[self._SaoOffsetPlane(s.buf_ptr, d.buf_ptr, s.stride, d.stride, s.width, s.height, cw, ch, bit_depth, lo, hi, 0)
+                                                      for (s, d), (cw, ch), (lo, hi) in zip(planes, ctu, clip)])
+        self._ck(self.L.vvhip_sao_offset(self.ctx, desc, len(planes), prm.ctypes.data_as(C.c_void_p), rows[0], rows[1]))
+        return [d for (_, d) in planes]
 
     # ---- SURVEY 8f rank 2: MCTF apply side ----
     REF_STRENGTHS = ((0.84375, 0.6, 0.4286, 0.3333, 0.2727, 0.2308), (1.12500, 1.0, 0.7143, 0.5556, 0.4545, 0.3846))      # MCTF.cpp:112-117
