@@ -611,7 +611,12 @@ VVHIP_API int vvhip_pred_inter_batch( vvhip_ctx* ctx, const vvhip_me_plane* plan
  * Argument errors (VVHIP_E_ARG with a message, nothing launched): BDOF on chroma, with one list or on a size that fails the rule; a delta out of range; unknown flag bits or
  * non-zero reserved bytes.  Everything vvhip_pred_inter_batch promises holds: order independence, the schedule cache (the extension array is part of the list's key),
  * the residual, both output layouts.  Margins: the BDOF ring lies one sample beyond the block, inside the 4-sample luma margin; a DMVR item reads inside the margin
- * of its START position.                                                                                                                                                  */
+ * of its START position.
+ * Bit depths 8..12.  Compared with the reference at 8, 10 and 12 bits (the reference's own xApplyBDOF on recorded frames, scalar and x86 row; the interpolation from the
+ * compiled reference).  Operand ranges established on planes of samples in [0, 2^bit_depth) (tests/test_oracle_pred_ext_extremes.py): the 14-bit block of a list within
+ * +-25 100 while its ring stays in [-8192, 8191]; |gradient| up to 519 (255 if the block were in the ring's range), |dI| up to 3135 (1023), |b| up to 16 425; tmpx and tmpy
+ * take every value of -15..15; the value in front of the (int16_t) cast and the final clip stays inside int16, so the cast never acts on frames made from planes; under
+ * VVHIP_PRED_EXT_DMVR_PAD every ring sample already lies inside the clamp window (|delta| <= 2 against a reach of 3).                                                     */
 #define VVHIP_PRED_EXT_BDOF     1
 #define VVHIP_PRED_EXT_DMVR_PAD 2
 typedef struct
@@ -643,7 +648,9 @@ VVHIP_API int vvhip_pred_inter_batch_ex( vvhip_ctx* ctx, const vvhip_me_plane* p
  * InterPrediction.cpp:478, :975).  Everything vvhip_pred_inter_batch promises holds: order independence, both output layouts, the residual, the schedule cache — the blend
  * array is part of the list's key, and a list with a blend array keeps a schedule of its own: alternating with vvhip_pred_inter_batch[_ex] and vvhip_pred_affine_batch on one
  * context evicts none of the three.
- * CIIP has a record of its own: vvhip_pred_inter_batch_ciip below.  Still the caller's: explicit weighted prediction, IBC.                                             */
+ * CIIP has a record of its own: vvhip_pred_inter_batch_ciip below.  Still the caller's: explicit weighted prediction, IBC.
+ * Bit depths 8..12; compared with the reference's addWeightedAvg / xWeightedGeoBlk (scalar and x86 row) at 8, 10 and 12 bits, on 0 / max checkerboards at half-sample
+ * fractions where the weights -2 / 10 drive both clip ends.                                                                                                              */
 #define VVHIP_PRED_BLEND_DEFAULT 0   /* exactly what the item does without a blend record     */
 #define VVHIP_PRED_BLEND_BCW     1   /* param = bcw_idx 0..4                                  */
 #define VVHIP_PRED_BLEND_GEO     2   /* param = geoSplitDir 0..63                             */
@@ -671,7 +678,9 @@ VVHIP_API int vvhip_pred_inter_batch_blend( vvhip_ctx* ctx, const vvhip_me_plane
  * result), the schedule cache — the CIIP array is part of the list's key, and a list with a CIIP array keeps a schedule of its own: alternating with
  * vvhip_pred_inter_batch[_ex], vvhip_pred_inter_batch_blend and vvhip_pred_affine_batch on one context evicts none of them.
  * Still the caller's: explicit weighted prediction, IBC, and CIIP in a picture with LMCS active (the forward luma mapping of the inter part before the weighting); of CIIP
- * itself the CU-level conditions, the reference line and num_intra.                                                                                                      */
+ * itself the CU-level conditions, the reference line and num_intra.
+ * Bit depths 8..12; compared with the reference's planar prediction, PDPC and weightCiip (scalar and x86 row) at 8, 10 and 12 bits, with lines all 0, all 2^bit_depth - 1
+ * and alternating, and with an inter part whose clip acts at both ends.                                                                                                   */
 #define VVHIP_PRED_CIIP_OFF 0   /* exactly what the item does without a CIIP record      */
 #define VVHIP_PRED_CIIP_ON  1   /* ref_off, num_intra as above                           */
 typedef struct { int32_t ref_off; uint8_t mode, num_intra, rsv[2]; } vvhip_pred_ciip;   /* 8 bytes, rsv zero */
@@ -704,7 +713,9 @@ VVHIP_API int vvhip_pred_inter_batch_ciip( vvhip_ctx* ctx, const vvhip_me_plane*
  * right of / below it (the + 1: PROF's ring) — with CUs no larger than the CTU inside the reference encoder's own picture margin of ctu_size + 16 —, plus the 16 bytes of the
  * aligned-dword rule; planes need an even row pitch.
  * Argument errors (VVHIP_E_ARG with a message naming the entry, nothing launched): a CU size that is not a power of two in 8..128; neither list used; a plane index outside the
- * table; chroma > 1; six_param > 1; prof > 3; non-zero reserved bytes; a control point outside the 18-bit vector range; ctu_size not 32 / 64 / 128; a CU outside the picture.  */
+ * table; chroma > 1; six_param > 1; prof > 3; non-zero reserved bytes; a control point outside the 18-bit vector range; ctu_size not 32 / 64 / 128; a CU outside the picture.
+ * Bit depths 8..12; compared with the reference's xPredAffineBlk (scalar and x86 row) at 8, 10 and 12 bits, with dMv at +-31 and dI in its clip.  That clip is 1 << 13 at
+ * every accepted bit depth ( max( bit_depth + 1, 13 ) = 13 up to 12 bits ).                                                                                                */
 typedef struct
 {
   int32_t dst_off;            /* sample offset of the block in d_pred (and in d_resi)                                  */
