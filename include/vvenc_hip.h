@@ -922,7 +922,7 @@ VVHIP_API int vvhip_ccalf_filter_plane( vvhip_ctx* ctx, int16_t* d_dst_c, ptrdif
 
 /* ======================================================================================================================
  * SAO (sample adaptive offset), the stage in front of ALF in the per-CTU pipeline CTU_ENCODE -> LF -> SAO -> ALF (EncoderLib/EncSlice.cpp:1058-1141): the statistics of a
- * picture and the offset filtering of a picture, each ONE launch for up to 3 planes and a band of CTU rows.  With both, a deblocked picture is uploaded once and stays in
+ * picture and the offset filtering of a picture, each ONE launch for up to 3 planes and a band of CTU rows.  With both, a deblocked picture stays in
  * HBM through to the ALF entries above.
  *   vvhip_sao_stats  <- EncSampleAdaptiveOffset::getBlkStats (EncoderLib/EncSampleAdaptiveOffset.cpp:810-929) + the five calcSaoStatistics*_Core routines
  *       (CommonLib/SampleAdaptiveOffset.cpp:281-399) for every CTU, as getStatistics (:294-344) and getCtuStatistics (:239-292) drive them.
@@ -988,6 +988,58 @@ typedef struct
 VVHIP_API int vvhip_sao_stats( vvhip_ctx* ctx, const vvhip_sao_stats_plane* planes, int n_planes, int ctu_row0, int n_rows, const uint8_t* flags_host /* may be NULL */,
                                int64_t* d_out );
 VVHIP_API int vvhip_sao_offset( vvhip_ctx* ctx, const vvhip_sao_offset_plane* planes, int n_planes, const vvhip_sao_param* params_host, int ctu_row0, int n_rows );
+
+/* ======================================================================================================================
+ * LF (the deblocking filter), the stage in front of SAO in the per-CTU pipeline CTU_ENCODE -> LF -> SAO -> ALF: with it the UNFILTERED reconstruction is uploaded once and
+ * everything up to ALF's output happens in HBM.
+ *   vvhip_deblock <- LoopFilter::xDeblockArea<EDGE_VER> over every CTU of the picture, then xDeblockArea<EDGE_HOR> over every CTU (CommonLib/LoopFilter.cpp:405-462, as
+ *       EncoderLib/EncSlice.cpp:1020 / :1052 run them), in place on d_plane, bit-exact:
+ *       luma   xEdgeFilterLuma (:1372-1520) per 4-sample edge segment of the 4 x 4 grid: bS = bs bits 0-1, qp[0], P / Q lengths = side_max_filt_length bits 4-6 / 0-2 (bit 7,
+ *              the transform-edge mark, is ignored); at a horizontal CTU boundary the P side is never long (:1437); tc / beta from sm_tcTable / sm_betaTable (:79-87) with
+ *              the bit-depth scaling of :1445-1446; the long-filter decision (xUseStrongFiltering, :1318-1370) and xFilteringPandQCore (:123-201) for the P / Q length
+ *              pairs 7/7, 7/5, 5/7, 7/3, 3/7, 5/5, 5/3, 3/5; otherwise d < beta, the side thresholds only where both lengths > 1, the strong filter only where both > 2, and
+ *              xPelFilterLumaCorePel (:217-264): strong, or weak with | delta | < 10 tc, the second samples, ClipPel to [clip_min, clip_max].
+ *       chroma xEdgeFilterChroma (:1522-1635), 4:2:0, only where the chroma position inside the CTU is a multiple of 8 across the edge (:449-452), two samples per record:
+ *              per component bS = bs bits 2-3 / 4-5, qp[1] / qp[2], the plane's own offsets; filtered where bS == 2, or bS == 1 with filterCMFL (flags bit 5); the
+ *              large-boundary decision with dp3 / dq3 one line on; at a horizontal CTB boundary the shortened P side (xCalcDP's p1 - 2 p1 + p0, :1305, and the four-sample
+ *              strong form of :301-304); xPelFilterChroma (:284-342) weak / strong.
+ *       The reference's bPartPNoFilter / bPartQNoFilter are constant false; there is no lossless bypass.
+ * Maps: lfp_ver_host / lfp_hor_host are HOST arrays of LoopFilterParam records (CommonLib/TypeDef.h:546-559; vvhip_lf_param is byte-compatible), one per 4 x 4 luma unit,
+ * lfp_stride records per map row (>= width / 4).  Only the band's records are read.  They are validated, copied and uploaded by the call; the copy a previous launch may
+ * still be reading is waited for first, so the caller's arrays are free when the call returns.  A map of a direction not in `dirs` may be NULL.
+ * The maps must be LEGAL, as calcFilterStrengths (:552-1271) leaves them: no edge of a direction writes a sample another edge of that direction reads or writes.  The entry
+ * cannot check that geometry; on other maps the result is undefined (but no sample outside width x height is read or written).
+ * Bands: CTU rows [ctu_row0, ctu_row0 + n_rows), dirs = any non-empty subset of VVHIP_DBK_VER | VVHIP_DBK_HOR.  VER filters every vertical edge whose samples lie in the
+ * band's rows.  HOR filters every horizontal edge with y in the band — the band's top CTU boundary included, so it may write up to 3 luma rows and 1 chroma row above the
+ * band, and nothing else outside it.  With both bits VER of the band completes before its HOR starts (two launches in stream order).
+ * CALLER'S CONTRACT: VER of CTU row r - 1 must have been issued (same stream, or ordered by events) before HOR of row r.  Under it every partition of a picture into bands
+ * gives the one-call result: bands top to bottom with both bits, or all VER bands in any order followed by all HOR bands in any order.
+ * Planes: n_planes 1 (4:0:0, or luma only) or 3 (4:2:0: planes 1, 2 exactly half of plane 0); any strides (in samples, >= width) and any base alignment; samples are read
+ * and written only inside width x height.  Results are identical from run to run.
+ * VVHIP_E_ARG, before any launch and with nothing written: n_planes not 1 or 3; chroma planes not exactly half the luma size; luma width or height no multiple of 8;
+ * bit_depth outside 8..12; ctu_size no power of two in 16..128; a band outside the picture or n_rows < 1; dirs outside 1..3; lfp_stride < width / 4; clip_min > clip_max;
+ * and in the band's records: a bs field of 3; a P or Q length outside { 0, 1, 2, 3, 5, 7 } where the luma bs is non-zero; flag bits other than 0, 1, 5; a non-zero bs in
+ * column 0 of the vertical map or row 0 of the horizontal map (the reference would read outside the picture).
+ * Still the caller's: calcFilterStrengths (serial, syntax-bound: CUs, TUs, motion) and the band ordering contract above.                                                     */
+typedef struct
+{
+  int8_t  qp[3];                   /* the edge's QP per component                                                 */
+  uint8_t bs;                      /* bS: bits 0-1 luma, 2-3 Cb, 4-5 Cr, each 0..2                                */
+  uint8_t side_max_filt_length;    /* luma: P length in bits 4-6, Q length in bits 0-2                            */
+  uint8_t flags;                   /* bits 0, 1: filterEdge per channel type (not read); bit 5: filterCMFL        */
+} vvhip_lf_param;                  /* 6 bytes, byte-compatible with LoopFilterParam */
+typedef struct
+{
+  int16_t* d_plane;                /* filtered in place                                                           */
+  int32_t stride, width, height;   /* stride in samples                                                           */
+  int32_t clip_min, clip_max;      /* ClpRng of the component (the weak filters' ClipPel)                         */
+  int32_t beta_offset_div2, tc_offset_div2;   /* the slice's deblockingFilterBetaOffsetDiv2 / TcOffsetDiv2 of the component */
+} vvhip_deblock_plane;             /* 40 bytes */
+#define VVHIP_DBK_VER 1
+#define VVHIP_DBK_HOR 2
+VVHIP_API int vvhip_deblock( vvhip_ctx* ctx, const vvhip_deblock_plane* planes, int n_planes /* 1 = 4:0:0 or luma only, 3 = 4:2:0 */, int bit_depth, int ctu_size /* luma, 16..128 */,
+                             const vvhip_lf_param* lfp_ver_host, const vvhip_lf_param* lfp_hor_host, int lfp_stride /* records per map row, >= width / 4 */,
+                             int ctu_row0, int n_rows, int dirs );
 
 #ifdef __cplusplus
 }

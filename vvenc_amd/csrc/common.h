@@ -82,8 +82,9 @@ struct vvhip_ctx
   // the same for the sub-block transform entries (sbt.hip): [0] vvhip_sbt_parts_batch, [1] vvhip_sbt_place_batch — slots of their own again, so that alternating them with the
   // joint Cb-Cr and the prediction entries on one context evicts none of theirs
   IctSched sbtSched[2];
-  // the per-call host arrays of the SAO entries (sao.hip): [0] the CTU flags of vvhip_sao_stats, [1] the CTU parameters of vvhip_sao_offset — device slot, the host copy the
-  // asynchronous upload reads, and the event recorded behind the launch that reads the slot
+  // the per-call host arrays of the SAO entries (sao.hip): [0] the CTU flags of vvhip_sao_stats, [1] the CTU parameters of vvhip_sao_offset — and of the deblocking entry
+  // (deblock.hip): [2] the band's loop-filter records of vvhip_deblock — device slot, the host copy the asynchronous upload reads, and the event recorded behind the launch
+  // that reads the slot
   struct SaoSlot
   {
     void*        d         = nullptr;
@@ -91,7 +92,7 @@ struct vvhip_ctx
     std::vector<unsigned char> blob;
     hipEvent_t   event     = nullptr;
     bool         eventRecorded = false;
-  } saoSlot[2];
+  } saoSlot[3];
   // how the host waits for the stream (vvhip_set_blocking_sync): false = hipStreamSynchronize (the runtime's low-latency wait), true = a blocking event — the calling thread
   // sleeps, which matters when the host's cores are all busy encoding
   bool         blockingSync = false;
@@ -108,6 +109,10 @@ inline hipError_t vvhip_wait_stream( vvhip_ctx* ctx )
 }
 
 int vvhip_fail( vvhip_ctx* ctx, int code, const char* fmt, ... );
+
+// sao.hip: a per-call host array -> a context slot (waits for the last launch that read the slot, then uploads asynchronously), and the mark behind the launch that reads it
+int saoUpload( vvhip_ctx* ctx, vvhip_ctx::SaoSlot& S, const void* data, size_t bytes );
+int saoMark( vvhip_ctx* ctx, vvhip_ctx::SaoSlot& S );
 
 #define VVHIP_CHECK_HIP( ctx, expr )                                                        \
   do { hipError_t e_ = ( expr );                                                            \

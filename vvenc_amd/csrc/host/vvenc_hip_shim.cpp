@@ -1570,6 +1570,72 @@ bool SaoOps::offsetPicture( const Pel* const src[3], const vvhip_sao_param* para
 
 SaoOps::~SaoOps() {}      // (device areas are released with the process, like ALFOps')
 
+// ------------------------------------------------------------------------------------------------ DeblockOps
+bool DeblockOps::begin( const int stride[3], int width, int height, int bitDepth, int ctuSize, const int betaOffsetDiv2[3], const int tcOffsetDiv2[3] )
+{
+  m_open = false;
+  if( width < 8 || height < 8 || ( width & 7 ) || ( height & 7 ) || ctuSize < 16 || ctuSize > 128 || ( ctuSize & ( ctuSize - 1 ) ) || bitDepth < 8 || bitDepth > 12 ) return false;
+  for( int c = 0; c < 3; c++ ) if( stride[c] < ( c ? width >> 1 : width ) ) return false;
+  Device& dev = Device::get();
+  size_t total = 0;
+  for( int c = 0; c < 3; c++ )
+  {
+    m_rp[c] = stride[c]; m_beta[c] = betaOffsetDiv2[c]; m_tc[c] = tcOffsetDiv2[c];
+    m_off[c] = total; total += ( ( size_t ) m_rp[c] * ( c ? height >> 1 : height ) + 127 ) & ~( size_t ) 127;
+  }
+  if( m_gpu != dev.gpu() || m_recElems < total )
+  {
+    if( m_dRec ) vvhip_free( dev.ctx(), m_dRec );
+    void* p = nullptr;
+    m_dRec = nullptr; m_recElems = 0;
+    dev.check( vvhip_malloc( dev.ctx(), &p, total * sizeof( Pel ) + 256 ), "deblocking planes" );
+    m_dRec = static_cast<int16_t*>( p ); m_recElems = total;
+  }
+  const int rows = ( height + ctuSize - 1 ) / ctuSize;
+  while( ( int ) m_events.size() < rows ) { void* e = nullptr; dev.check( vvhip_event_create( dev.ctx(), &e ), "deblocking band mark" ); m_events.push_back( e ); }
+  m_gpu = dev.gpu(); m_rows = rows; m_issued = 0; m_width = width; m_height = height; m_bitDepth = bitDepth; m_ctuSize = ctuSize; m_lastCtx = nullptr;
+  m_open = true;
+  return true;
+}
+
+bool DeblockOps::band( int ctuRow, const Pel* const rec[3], const vvhip_lf_param* lfpVer, const vvhip_lf_param* lfpHor, int lfpStride )
+{
+  Device& dev = Device::get();
+  if( !m_open || ctuRow != m_issued || ctuRow >= m_rows || dev.gpu() != m_gpu || !lfpVer || !lfpHor ) return false;
+  // another thread's stream issued the row above: its vertical edges must be done before this row's horizontal ones read them
+  if( ctuRow > 0 && m_lastCtx != dev.ctx() ) dev.check( vvhip_event_wait( dev.ctx(), m_events[ctuRow - 1] ), "deblocking band mark" );
+  vvhip_deblock_plane pl[3];
+  for( int c = 0; c < 3; c++ )
+  {
+    const int w = c ? m_width >> 1 : m_width, h = c ? m_height >> 1 : m_height, cs = c ? m_ctuSize >> 1 : m_ctuSize;
+    const int y0 = ctuRow * cs, bh = std::min( cs, h - y0 );
+    dev.check( vvhip_upload( dev.ctx(), m_dRec + m_off[c] + ( size_t ) y0 * m_rp[c], rec[c] + ( ptrdiff_t ) y0 * m_rp[c], ( ( size_t ) m_rp[c] * ( bh - 1 ) + w ) * sizeof( Pel ) ), "deblocking rec band" );
+    pl[c].d_plane = m_dRec + m_off[c]; pl[c].stride = m_rp[c]; pl[c].width = w; pl[c].height = h; pl[c].clip_min = 0; pl[c].clip_max = ( 1 << m_bitDepth ) - 1;
+    pl[c].beta_offset_div2 = m_beta[c]; pl[c].tc_offset_div2 = m_tc[c];
+  }
+  dev.check( vvhip_deblock( dev.ctx(), pl, 3, m_bitDepth, m_ctuSize, lfpVer, lfpHor, lfpStride, ctuRow, 1, VVHIP_DBK_VER | VVHIP_DBK_HOR ), "vvhip_deblock (band)" );
+  dev.check( vvhip_event_record( dev.ctx(), m_events[ctuRow] ), "deblocking band mark" );
+  m_lastCtx = dev.ctx(); m_issued++;
+  return true;
+}
+
+bool DeblockOps::end( Pel* const dst[3], const int dstStride[3] )
+{
+  if( !m_open || m_issued != m_rows ) return false;
+  Device& dev = Device::get();
+  if( dev.gpu() != m_gpu ) return false;
+  for( int c = 0; c < 3; c++ ) if( dst[c] && dstStride[c] < ( c ? m_width >> 1 : m_width ) ) return false;
+  for( int r = 0; r < m_rows; r++ ) dev.check( vvhip_event_wait( dev.ctx(), m_events[r] ), "deblocking band mark" );
+  for( int c = 0; c < 3; c++ )
+  {
+    const int w = c ? m_width >> 1 : m_width, h = c ? m_height >> 1 : m_height;
+    if( dst[c] ) dev.check( vvhip_download_2d( dev.ctx(), dst[c], ( size_t ) dstStride[c] * sizeof( Pel ), m_dRec + m_off[c], ( size_t ) m_rp[c] * sizeof( Pel ), ( size_t ) w * sizeof( Pel ), ( size_t ) h ), "deblocked plane" );
+  }
+  return true;
+}
+
+DeblockOps::~DeblockOps() {}      // (device areas are released with the process, like ALFOps')
+
 bool ALFOps::getStatisticsCcAlf( const Pel* orgC, int orgStride, const Pel* slfC, int slfStride, const Pel* recLuma, int recStride, int widthC, int heightC, int ctuSizeC,
                                  int vbCTUHeight, int vbPos, int picHeight, float* out, const float* init )
 {

@@ -404,6 +404,34 @@ private:
   std::vector<void*> m_events; std::vector<char> m_done;
 };
 
+// The deblocking filter of a picture (vvhip_deblock), 4:2:0: LoopFilter::xDeblockArea<EDGE_VER> / <EDGE_HOR> (CommonLib/LoopFilter.cpp:405-462) for whole CTU rows, on planes
+// that are uploaded UNFILTERED and stay in HBM.  calcFilterStrengths — serial, syntax-bound — stays with the encoder: it fills the two LoopFilterParam maps a band takes.
+struct DeblockOps
+{
+  // begin sets the picture up (any thread): line pitches of the reconstruction planes, luma size (multiples of 8), bit depth, luma CTU size (16..128, a power of two), the
+  // slice's deblockingFilterBetaOffsetDiv2 / TcOffsetDiv2 per component.  The clip range is [0, 2^bitDepth - 1].
+  // band( r ) uploads CTU row r of the three unfiltered planes from the encoder's planes and the row's records of both maps (lfpStride records per map row; the maps'
+  // first record is that of the picture's first unit) and filters the row — its vertical edges, then its horizontal edges, the row's top CTU boundary included — all
+  // asynchronous on the CALLING thread's stream, completion marked by an event.  Bands come top to bottom, each exactly once (the horizontal edges of a row read the
+  // row above after ITS vertical edges: vvenc_hip.h, the caller's contract of vvhip_deblock); a band issued by another thread than the one before waits for that band's mark.
+  // end waits for the marks and downloads the filtered planes: dst[c] (line pitch dstStride[c]; may be NULL: nothing is downloaded); false: not every band was issued.
+  // The filtered planes stay in HBM (residentPlane) for the SAO entries.
+  bool begin( const int stride[3], int width, int height, int bitDepth, int ctuSize, const int betaOffsetDiv2[3], const int tcOffsetDiv2[3] );
+  int  bands() const { return m_rows; }
+  bool band( int ctuRow, const Pel* const rec[3], const vvhip_lf_param* lfpVer, const vvhip_lf_param* lfpHor, int lfpStride );
+  bool end( Pel* const dst[3], const int dstStride[3] );
+  const int16_t* residentPlane( int c ) const { return m_dRec ? m_dRec + m_off[c] : nullptr; }      // device pointer, line pitch = stride[c]
+  ~DeblockOps();
+private:
+  bool m_open = false;
+  int m_gpu = -1, m_rows = 0, m_issued = 0, m_width = 0, m_height = 0, m_bitDepth = 0, m_ctuSize = 0;
+  int m_rp[3] = { 0, 0, 0 }, m_beta[3] = { 0, 0, 0 }, m_tc[3] = { 0, 0, 0 };
+  size_t m_off[3] = { 0, 0, 0 }, m_recElems = 0;
+  int16_t* m_dRec = nullptr;
+  const void* m_lastCtx = nullptr;
+  std::vector<void*> m_events;
+};
+
 // MCTF table, CommonLib/MCTF.h:160-170
 struct MCTFOps
 {

@@ -261,6 +261,9 @@ saoOffsetKernel( const SaoOffsetArgs a )
     }
 }
 
+} // namespace
+
+// (shared with deblock.hip: declared in common.h)
 // the per-call host array of an entry -> the context's device slot: grow-only, the host copy stays alive as the source of the asynchronous upload, and the event of the
 // last launch that read the slot is waited for before either is rewritten
 int saoUpload( vvhip_ctx* ctx, vvhip_ctx::SaoSlot& S, const void* data, size_t bytes )
@@ -289,6 +292,8 @@ int saoMark( vvhip_ctx* ctx, vvhip_ctx::SaoSlot& S )
   S.eventRecorded = true;
   return VVHIP_OK;
 }
+
+namespace {
 
 // the geometry rules both entries share; -> the CTU grid
 bool saoGrid( int width, int height, int ctuW, int ctuH, int stride, int* ctusX, int* ctusY )

@@ -106,6 +106,8 @@ SAO_LEFT, SAO_ABOVE, SAO_ABOVE_LEFT, SAO_RIGHT, SAO_BELOW, SAO_ABOVE_RIGHT = 1, 
 # the reference's availability mask of the filter (SampleAdaptiveOffset.h:75-85)
 SAO_AVAIL_LEFT, SAO_AVAIL_RIGHT, SAO_AVAIL_ABOVE, SAO_AVAIL_BELOW, SAO_AVAIL_ABOVE_LEFT, SAO_AVAIL_ABOVE_RIGHT, SAO_AVAIL_BELOW_LEFT, SAO_AVAIL_BELOW_RIGHT = 1, 2, 4, 8, 16, 32, 64, 128
 SAO_REC = 320      # VVHIP_SAO_REC: int64 per CTU and plane, [5][2][32] = SAOStatData[5]
+LF_PARAM_DTYPE = np.dtype([("qp", "i1", (3,)), ("bs", "u1"), ("side_max_filt_length", "u1"), ("flags", "u1")])      # vvhip_lf_param (6 bytes) = LoopFilterParam
+DBK_VER, DBK_HOR = 1, 2      # VVHIP_DBK_*
 SBT_MAX_DIST = (1 << 64) - 1      # MAX_DISTORTION: the estimate of a mode whose type is not allowed
 
 
@@ -795,6 +797,31 @@ class HotPath:
                                                       for (s, d), (cw, ch), (lo, hi) in zip(planes, ctu, clip)])
         self._ck(self.L.vvhip_sao_offset(self.ctx, desc, len(planes), prm.ctypes.data_as(C.c_void_p), rows[0], rows[1]))
         return [d for (_, d) in planes]
+
+    # ---- LF: the deblocking filter of a picture (deblock.hip) ----
+    class _DeblockPlane(C.Structure):
+        _fields_ = [("d_plane", C.c_void_p), ("stride", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("clip_min", C.c_int32), ("clip_max", C.c_int32),
+                    ("beta_offset_div2", C.c_int32), ("tc_offset_div2", C.c_int32)]
+
+    def deblock(self, planes, lfp_ver, lfp_hor, ctu_size, bit_depth, rows=None, dirs=3, clip=None, beta_offsets=(0, 0, 0), tc_offsets=(0, 0, 0)):
+        """xDeblockArea<EDGE_VER> then <EDGE_HOR> over the CTUs of CTU rows `rows` = ( first, count ) (None: the picture), in place.  planes: [ luma ] or [ luma, cb, cr ]
+        (4:2:0), Plane or PlaneView; lfp_ver / lfp_hor: LF_PARAM_DTYPE [ units down ][ units across ], one record per 4 x 4 luma unit (a map of a direction not in `dirs`
+        may be None); clip: per plane ( min, max ), None = ( 0, 2^bit_depth - 1 ); the offsets are the slice's per component.  The band contract: vvenc_hip.h"""
+        gy = -(-planes[0].height // ctu_size)
+        rows = (0, gy) if rows is None else rows
+        clip = [(0, (1 << bit_depth) - 1)] * len(planes) if clip is None else clip
+        maps, stride = [], 0
+        for m in (lfp_ver, lfp_hor):
+            if m is not None:
+                m = np.ascontiguousarray(m, LF_PARAM_DTYPE)
+                assert m.ndim == 2 and (stride in (0, m.shape[1])), "the maps are 2-D and have one line pitch"
+                stride = m.shape[1]
+            maps.append(m)
+        desc = (self._DeblockPlane * len(planes))(*[self._DeblockPlane(p.buf_ptr, p.stride, p.width, p.height, lo, hi, bo, to)
+                                                    for p, (lo, hi), bo, to in zip(planes, clip, beta_offsets, tc_offsets)])
+        self._ck(self.L.vvhip_deblock(self.ctx, desc, len(planes), bit_depth, ctu_size, *[m.ctypes.data_as(C.c_void_p) if m is not None else None for m in maps], stride,
+                                      rows[0], rows[1], dirs))
+        return planes
 
     # ---- SURVEY 8f rank 2: MCTF apply side ----
     REF_STRENGTHS = ((0.84375, 0.6, 0.4286, 0.3333, 0.2727, 0.2308), (1.12500, 1.0, 0.7143, 0.5556, 0.4545, 0.3846))      # MCTF.cpp:112-117
