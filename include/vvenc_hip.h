@@ -1041,6 +1041,51 @@ VVHIP_API int vvhip_deblock( vvhip_ctx* ctx, const vvhip_deblock_plane* planes, 
                              const vvhip_lf_param* lfp_ver_host, const vvhip_lf_param* lfp_hor_host, int lfp_stride /* records per map row, >= width / 4 */,
                              int ctu_row0, int n_rows, int dirs );
 
+/* ======================================================================================================================
+ * QPA (perceptual QP adaptation): the visual activity of the ORIGINAL picture — the one picture-level, decision-free stage in front of the CTU tasks.  Its inputs are fixed
+ * before any decision (the original plane and the two previous originals, the planes the MCTF entries already keep in HBM); its results are integer sums.
+ *   vvhip_visact <- the six high-pass entries of g_pelBufOP (CommonLib/Buffer.cpp:323-435, Buffer.h:123-128) as calcSpatialVisAct (EncoderLib/BitAllocation.cpp:84-117) and
+ *       calcTemporalVisAct (:119-195) call them, and the accumulator of AreaBuf::getAvg (CommonLib/Buffer.h:303-315), for a LIST of areas in one call:
+ *       the CTU areas of BitAllocation::applyQPAdaptationSlice (:553-573: the CTU plus a guard frame of 1 or 2 samples, and the clipped CTU for the mean), the whole chroma
+ *       planes (:610-616), the whole planes of PreProcess::xGetVisualActivity (EncoderLib/PreProcess.cpp:312-427), the sub-CTU areas of applyQPAdaptationSubCtu.
+ * Per area, d_out[4 * i + ..] (uint64):
+ *   [0] the spatial sum saAct.  ds == 0: AvgHighPass (Buffer.cpp:323-337) — | 12 c - 2 ( l + r + u + d ) - ( ul + ur + dl + dr ) | over 1 <= x <= w - 2, 1 <= y <= h - 2 of
+ *       the area (calcSpatialVisAct's skipped first row is the y = 0 the loop starts behind).  ds == 1: AvgHighPassWithDownsampling (:371-392) — the 6 x 6 kernel on the 2 x 2
+ *       cells at even x, y in 2 <= x < w - 2, 2 <= y < h - 2 RELATIVE TO THE AREA'S ORIGIN (what the reference uses where min( width, height ) of the source > 1280).
+ *   [1] the temporal sum taAct over the same positions (ds: the same cells, on the 2 x 2 cell sums): order 1 — HDHighPass / AvgHighPassWithDownsamplingDiff1st:
+ *       ( 1 + 3 | cur - prev1 | ) >> 1; order 2 — HDHighPass2 / AvgHighPassWithDownsamplingDiff2nd: | cur - 2 prev1 + prev2 |; order 0: 0.
+ *   [2] the plain sample sum of the mean rectangle ( mx, my, mw, mh ) of the plane's cur (two's complement; 0 where mw == 0): getAvg's acc.
+ *   [3] the number of positions summed into [0]: ( w - 2 ) ( h - 2 ), or ( w - 4 ) / 2 * ( h - 4 ) / 2.
+ * Every record is written completely, nothing else is.  Areas may overlap, be a whole plane, come in any order; an area's record depends on nothing but the area.  All sums are
+ * integers: results are identical from run to run (no atomics).  Samples are int16; the sums are exact for ANY int16 samples, bit_depth only documents the plane.
+ * areas_host is a HOST array, validated, cut into tiles and uploaded by the call (the copy a previous launch may still read is waited for first); planes is read by the call.
+ * VVHIP_E_ARG, before any launch and with nothing written: n < 0; n_planes outside 1..3; a plane without d_cur, with a stride < width, width or height < 1 or bit_depth outside
+ * 8..16; a plane index outside the table; an area or a mean rectangle not inside its plane (mw > 0 needs mh > 0 and the reverse); ds == 0 with w < 3 or h < 3; ds == 1 with
+ * w < 6 or h < 6 or an odd w or h (the reference's loop would read a row / column beyond the area); ds > 1; order > 2; order >= 1 with d_prev1 == NULL, order == 2 with
+ * d_prev2 == NULL (or a stride < width of a plane an area uses); non-zero reserved bytes.  n == 0 succeeds and launches nothing.
+ * Still the caller's (out of scope here): hooking the entry into the running encoder; the doubles made of the sums — hpSpatAct, hpTempAct, the 1.15625 factor, the
+ * pS0 == pSM1 bypass, updateVisAct (the shim's VisActOps restates them) — and everything in applyQPAdaptationSlice behind the sums (apprI3Log2, the glaring-colour offset,
+ * noise levels, peak smoothing, rate control); getCtuPumpingReducingQP; the film-grain analyser.                                                                            */
+typedef struct
+{
+  const int16_t* d_cur;            /* the original plane                                                          */
+  const int16_t* d_prev1;          /* the previous original (PREV_FRAME_1), may be NULL                           */
+  const int16_t* d_prev2;          /* the one before (PREV_FRAME_2), may be NULL                                  */
+  int32_t cur_stride, prev1_stride, prev2_stride;      /* in samples                                              */
+  int32_t width, height, bit_depth;
+} vvhip_visact_plane;              /* 48 bytes */
+typedef struct
+{
+  uint8_t plane;                   /* row of the plane table                                                      */
+  uint8_t ds;                      /* 0: the HD form, 1: the down-sampling form                                   */
+  uint8_t order;                   /* 0: no temporal part, 1: first order, 2: second order                        */
+  uint8_t rsv0;                    /* 0                                                                           */
+  int32_t x, y, w, h;              /* the filter area, in samples of the plane                                    */
+  int32_t mx, my, mw, mh;          /* the mean rectangle, in samples of the plane; mw == 0: none                  */
+  int32_t rsv1;                    /* 0                                                                           */
+} vvhip_visact_area;               /* 40 bytes */
+VVHIP_API int vvhip_visact( vvhip_ctx* ctx, const vvhip_visact_plane* planes, int n_planes, const vvhip_visact_area* areas_host, int n, uint64_t* d_out /* [n][4] */ );
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,7 +84,7 @@ struct vvhip_ctx
   IctSched sbtSched[2];
   // the per-call host arrays of the SAO entries (sao.hip): [0] the CTU flags of vvhip_sao_stats, [1] the CTU parameters of vvhip_sao_offset — and of the deblocking entry
   // (deblock.hip): [2] the band's loop-filter records of vvhip_deblock — device slot, the host copy the asynchronous upload reads, and the event recorded behind the launch
-  // that reads the slot
+  // that reads the slot — and of the visual-activity entry (visact.hip): [3] the tile list and area table of vvhip_visact, [4] its per-tile partial records (device only)
   struct SaoSlot
   {
     void*        d         = nullptr;
@@ -92,7 +92,7 @@ struct vvhip_ctx
     std::vector<unsigned char> blob;
     hipEvent_t   event     = nullptr;
     bool         eventRecorded = false;
-  } saoSlot[3];
+  } saoSlot[5];
   // how the host waits for the stream (vvhip_set_blocking_sync): false = hipStreamSynchronize (the runtime's low-latency wait), true = a blocking event — the calling thread
   // sleeps, which matters when the host's cores are all busy encoding
   bool         blockingSync = false;

@@ -1636,6 +1636,117 @@ bool DeblockOps::end( Pel* const dst[3], const int dstStride[3] )
 
 DeblockOps::~DeblockOps() {}      // (device areas are released with the process, like ALFOps')
 
+// ------------------------------------------------------------------------------------------------ VisActOps
+bool VisActOps::picture( int nPlanes, const Pel* const cur[], const Pel* const prev1[], const Pel* const prev2[], const int curStride[], const int prev1Stride[],
+                         const int prev2Stride[], const int width[], const int height[], int bitDepth )
+{
+  m_open = false;
+  if( nPlanes < 1 || nPlanes > 3 || bitDepth < 8 || bitDepth > 16 ) return false;
+  size_t total = 0;
+  for( int c = 0; c < nPlanes; c++ )
+  {
+    if( !cur[c] || width[c] < 1 || height[c] < 1 || curStride[c] < width[c] || ( prev1[c] && prev1Stride[c] < width[c] ) || ( prev2[c] && prev2Stride[c] < width[c] ) ) return false;
+    total += 3 * ( ( ( size_t ) width[c] * height[c] + 127 ) & ~( size_t ) 127 );
+  }
+  Device& dev = Device::get();
+  if( m_gpu != dev.gpu() || m_elems < total )
+  {
+    if( m_d ) vvhip_free( dev.ctx(), m_d );
+    void* p = nullptr;
+    m_d = nullptr; m_elems = 0;
+    dev.check( vvhip_malloc( dev.ctx(), &p, total * sizeof( Pel ) + 256 ), "visual-activity planes" );
+    m_d = static_cast<int16_t*>( p ); m_elems = total;
+  }
+  if( m_gpu != dev.gpu() ) { m_dOut = nullptr; m_outRecs = 0; }      // (an area of another GPU is released with the process)
+  size_t at = 0;
+  for( int c = 0; c < nPlanes; c++ )
+  {
+    const size_t slot = ( ( size_t ) width[c] * height[c] + 127 ) & ~( size_t ) 127, pitch = ( size_t ) width[c] * sizeof( Pel );
+    const Pel* src[3] = { cur[c], prev1[c], prev2[c] };
+    const int  str[3] = { curStride[c], prev1Stride[c], prev2Stride[c] };
+    m_same[c] = prev1[c] == cur[c];
+    for( int k = 0; k < 3; k++, at += slot )
+    {
+      m_pl[c][k] = nullptr;
+      if( !src[k] ) continue;
+      if( k == 1 && m_same[c] ) { m_pl[c][1] = m_pl[c][0]; continue; }
+      dev.check( vvhip_upload_2d( dev.ctx(), m_d + at, pitch, src[k], ( size_t ) str[k] * sizeof( Pel ), pitch, ( size_t ) height[c] ), "visual-activity plane" );
+      m_pl[c][k] = m_d + at;
+    }
+    m_w[c] = width[c]; m_h[c] = height[c];
+  }
+  dev.check( vvhip_sync( dev.ctx() ), "visual-activity planes" );      // the caller's planes are free when this returns
+  m_gpu = dev.gpu(); m_n = nPlanes; m_bitDepth = bitDepth; m_areas.clear(); m_rec.clear();
+  m_open = true;
+  return true;
+}
+
+bool VisActOps::sums( const vvhip_visact_area* areas, int n )
+{
+  Device& dev = Device::get();
+  if( !m_open || dev.gpu() != m_gpu || !areas || n < 1 ) return false;
+  if( m_outRecs < ( size_t ) n )
+  {
+    if( m_dOut ) vvhip_free( dev.ctx(), m_dOut );
+    void* p = nullptr;
+    m_dOut = nullptr; m_outRecs = 0;
+    dev.check( vvhip_malloc( dev.ctx(), &p, ( size_t ) n * 4 * sizeof( uint64_t ) ), "visual-activity records" );
+    m_dOut = static_cast<uint64_t*>( p ); m_outRecs = n;
+  }
+  vvhip_visact_plane pl[3];
+  for( int c = 0; c < m_n; c++ )
+  {
+    pl[c].d_cur = m_pl[c][0]; pl[c].d_prev1 = m_pl[c][1]; pl[c].d_prev2 = m_pl[c][2];
+    pl[c].cur_stride = pl[c].prev1_stride = pl[c].prev2_stride = m_w[c];
+    pl[c].width = m_w[c]; pl[c].height = m_h[c]; pl[c].bit_depth = m_bitDepth;
+  }
+  dev.check( vvhip_visact( dev.ctx(), pl, m_n, areas, n, m_dOut ), "vvhip_visact" );
+  m_rec.assign( ( size_t ) n * 4, 0 );
+  dev.check( vvhip_download( dev.ctx(), m_rec.data(), m_dOut, m_rec.size() * sizeof( uint64_t ) ), "visual-activity records" );
+  m_areas.assign( areas, areas + n );
+  return true;
+}
+
+// calcSpatialVisAct, calcTemporalVisAct and updateVisAct (EncoderLib/BitAllocation.cpp:84-204) behind the table entries' sums: the reference's own double expressions, in
+// its order (this file is compiled without contraction: hpSpatAct + 2.0 * hpTempAct is a product and a sum, as on the reference's x86-64 build)
+VisAct VisActOps::fromRecord( const uint64_t rec[4], int width, int height, uint32_t bitDepth, bool isUHD, int order, bool prev1IsCur )
+{
+  VisAct va;
+  const uint64_t saAct = rec[0], taAct = rec[1];
+  if( isUHD ) va.hpSpatAct = double( saAct ) / double( ( width - 4 ) * ( height - 4 ) );
+  else        va.hpSpatAct = double( saAct ) / double( ( width - 2 ) * ( height - 2 ) );
+  va.spatAct = unsigned( 0.5 + va.hpSpatAct * double( bitDepth < 12 ? 1 << ( 12 - bitDepth ) : 1 ) );
+  if( order > 0 )
+  {
+    const uint32_t frameRate = order == 2 ? 32 : 24;      // ( force 1st-order delta if only prev. frame available: frameRate = 24 )
+    if( prev1IsCur && frameRate <= 31 ) va.hpTempAct = 0;      // bypass high-pass, result will be zero
+    else if( isUHD ) va.hpTempAct = double( taAct ) / double( ( width - 4 ) * ( height - 4 ) );
+    else             va.hpTempAct = double( taAct ) / double( ( width - 2 ) * ( height - 2 ) );
+    va.tempAct = unsigned( 0.5 + va.hpTempAct * double( bitDepth < 12 ? 1 << ( 12 - bitDepth ) : 1 ) * ( frameRate <= 31 ? 1.15625 : 1.0 ) );
+  }
+  va.minAct = std::min( va.tempAct, va.spatAct );
+  va.hpVisAct = std::max( double( 1 << ( bitDepth - 6 ) ), va.hpSpatAct + 2.0 * va.hpTempAct );
+  const uint16_t v = uint16_t( 0.5 + va.hpVisAct ), top = uint16_t( ( 1 << bitDepth ) - 1 );
+  va.visAct = v > top ? top : v;      // ClipBD( uint16_t( .. ), bitDepth )
+  return va;
+}
+
+VisAct VisActOps::visAct( int i ) const
+{
+  const vvhip_visact_area& a = m_areas.at( i );
+  return fromRecord( record( i ), a.w, a.h, m_bitDepth, a.ds != 0, a.order, m_same[a.plane] );
+}
+
+int VisActOps::avg( int i ) const
+{
+  const vvhip_visact_area& a = m_areas.at( i );
+  if( a.mw <= 0 ) return -1;
+  const int64_t acc = ( int64_t ) record( i )[2], area = ( int64_t ) a.mw * a.mh;
+  return ( int ) Pel( ( acc + ( area >> 1 ) ) / area );
+}
+
+VisActOps::~VisActOps() {}      // (device areas are released with the process, like ALFOps')
+
 bool ALFOps::getStatisticsCcAlf( const Pel* orgC, int orgStride, const Pel* slfC, int slfStride, const Pel* recLuma, int recStride, int widthC, int heightC, int ctuSizeC,
                                  int vbCTUHeight, int vbPos, int picHeight, float* out, const float* init )
 {

@@ -432,6 +432,44 @@ private:
   std::vector<void*> m_events;
 };
 
+// The visual activity of the original picture for perceptual QP adaptation (vvhip_visact): the sums of the six high-pass entries of g_pelBufOP (CommonLib/Buffer.h:123-128)
+// and of AreaBuf::getAvg for a list of areas, and what calcSpatialVisAct / calcTemporalVisAct / updateVisAct (EncoderLib/BitAllocation.cpp:84-204) make of them.  Everything
+// in applyQPAdaptationSlice behind the sums — apprI3Log2, the glaring-colour offset, noise levels, peak smoothing, rate control — stays with the encoder.
+struct VisAct      // EncoderLib/BitAllocation.h:57-77
+{
+  double   hpSpatAct = 0.0, hpTempAct = 0.0, hpVisAct = 0.0;
+  unsigned spatAct = 0, tempAct = 0, visAct = 0, minAct = 0;
+};
+struct VisActOps
+{
+  // picture uploads the original planes of up to three components and their two previous originals (any thread; host line pitches per pointer; prev1[c] / prev2[c] may be
+  // NULL; prev1[c] == cur[c] — the first picture — is not uploaded twice and takes the reference's pS0 == pSM1 bypass).  The planes stay in HBM (residentPlane) until the
+  // next picture: any number of lists may be summed on them — the CTU list of slice initialisation, the whole planes of pre-processing, sub-CTU areas.
+  // sums runs vvhip_visact on a list and downloads the records; false: no picture, one on another GPU, or n < 1.  An illegal list throws like every failed entry.
+  bool picture( int nPlanes, const Pel* const cur[], const Pel* const prev1[], const Pel* const prev2[], const int curStride[], const int prev1Stride[], const int prev2Stride[],
+                const int width[], const int height[], int bitDepth );
+  bool sums( const vvhip_visact_area* areas, int n );
+  int  count() const { return ( int ) m_areas.size(); }
+  const uint64_t* record( int i ) const { return m_rec.data() + 4 * ( size_t ) i; }      // saAct, taAct, getAvg's accumulator, positions
+  // the VisAct of area i as filterAndCalculateAverageActivity leaves it: order 1 is a frame rate <= 31 (the 1.15625 factor), order 2 one above it, order 0 leaves the
+  // temporal fields 0; bit for bit the reference's doubles
+  VisAct visAct( int i ) const;
+  int    avg( int i ) const;      // AreaBuf<Pel>::getAvg of the mean rectangle; -1 where the area has none
+  static VisAct fromRecord( const uint64_t rec[4], int width, int height, uint32_t bitDepth, bool isUHD, int order, bool prev1IsCur );
+  const int16_t* residentPlane( int c, int which ) const { return m_d ? m_pl[c][which] : nullptr; }      // device pointer (which: 0 cur, 1 prev1, 2 prev2), line pitch = width[c]
+  ~VisActOps();
+private:
+  bool m_open = false;
+  int m_gpu = -1, m_n = 0, m_bitDepth = 0;
+  int m_w[3] = { 0, 0, 0 }, m_h[3] = { 0, 0, 0 };
+  bool m_same[3] = { false, false, false };
+  size_t m_elems = 0, m_outRecs = 0;
+  int16_t* m_d = nullptr; const int16_t* m_pl[3][3] = { { nullptr, nullptr, nullptr }, { nullptr, nullptr, nullptr }, { nullptr, nullptr, nullptr } };
+  uint64_t* m_dOut = nullptr;
+  std::vector<vvhip_visact_area> m_areas;
+  std::vector<uint64_t> m_rec;
+};
+
 // MCTF table, CommonLib/MCTF.h:160-170
 struct MCTFOps
 {

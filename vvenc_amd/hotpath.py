@@ -108,6 +108,8 @@ SAO_AVAIL_LEFT, SAO_AVAIL_RIGHT, SAO_AVAIL_ABOVE, SAO_AVAIL_BELOW, SAO_AVAIL_ABO
 SAO_REC = 320      # VVHIP_SAO_REC: int64 per CTU and plane, [5][2][32] = SAOStatData[5]
 LF_PARAM_DTYPE = np.dtype([("qp", "i1", (3,)), ("bs", "u1"), ("side_max_filt_length", "u1"), ("flags", "u1")])      # vvhip_lf_param (6 bytes) = LoopFilterParam
 DBK_VER, DBK_HOR = 1, 2      # VVHIP_DBK_*
+VISACT_AREA_DTYPE = np.dtype([("plane", "u1"), ("ds", "u1"), ("order", "u1"), ("rsv0", "u1"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"),
+                              ("mx", "<i4"), ("my", "<i4"), ("mw", "<i4"), ("mh", "<i4"), ("rsv1", "<i4")])      # vvhip_visact_area (40 bytes)
 SBT_MAX_DIST = (1 << 64) - 1      # MAX_DISTORTION: the estimate of a mode whose type is not allowed
 
 
@@ -822,6 +824,49 @@ class HotPath:
         self._ck(self.L.vvhip_deblock(self.ctx, desc, len(planes), bit_depth, ctu_size, *[m.ctypes.data_as(C.c_void_p) if m is not None else None for m in maps], stride,
                                       rows[0], rows[1], dirs))
         return planes
+
+    # ---- QPA: the visual activity of the original picture (visact.hip) ----
+    class _VisActPlane(C.Structure):
+        _fields_ = [("d_cur", C.c_void_p), ("d_prev1", C.c_void_p), ("d_prev2", C.c_void_p), ("cur_stride", C.c_int32), ("prev1_stride", C.c_int32), ("prev2_stride", C.c_int32),
+                    ("width", C.c_int32), ("height", C.c_int32), ("bit_depth", C.c_int32)]
+
+    def visact(self, planes, areas, out=None):
+        """the high-pass sums of calcSpatialVisAct / calcTemporalVisAct and getAvg's sample sum for a list of areas in one call.  planes: up to three table rows
+        ( cur, prev1, prev2, bit_depth ), Plane or PlaneView, prev1 / prev2 may be None; areas: VISACT_AREA_DTYPE [ n ].  -> int64 tensor ( n, 4 ) holding the uint64 records
+        [ spatial sum, temporal sum, sample sum of the mean rectangle, positions ] (vvenc_hip.h); with out given, only its first n rows are written"""
+        ar = np.ascontiguousarray(areas, VISACT_AREA_DTYPE).reshape(-1)
+        if out is None:
+            out = torch.zeros((ar.size, 4), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.int64 and out.numel() >= 4 * ar.size
+        desc = (self._VisActPlane * len(planes))(*[self._VisActPlane(c.buf_ptr, p1.buf_ptr if p1 is not None else None, p2.buf_ptr if p2 is not None else None, c.stride,
+                                                                     p1.stride if p1 is not None else 0, p2.stride if p2 is not None else 0, c.width, c.height, bd)
+                                                   for (c, p1, p2, bd) in planes])
+        self._ck(self.L.vvhip_visact(self.ctx, desc, len(planes), ar.ctypes.data_as(C.c_void_p), ar.size, _ptr(out)))
+        return out
+
+    @staticmethod
+    def visact_picture_areas(sizes, ctu, high_res, order, chroma="420"):
+        """the reference's own area list of a picture (BitAllocation.cpp:553-573, :610-616).  sizes: ( width, height ) per component -> VISACT_AREA_DTYPE: per CTU of plane 0,
+        in raster order, the CTU with its guard frame of 1 (2 with high_res) samples, clipped to the picture, with the clipped CTU as the mean rectangle; then one whole-plane
+        area per component (the plane is its own mean rectangle).  high_res selects the down-sampling form — for the chroma planes only with chroma == "444" """
+        W, H = sizes[0]
+        guard, out = (2 if high_res else 1), []
+        for y in range(0, H, ctu):
+            for x in range(0, W, ctu):
+                fx, fy = (x - guard if x > 0 else 0), (y - guard if y > 0 else 0)
+                fw, fh = ctu + guard * (2 if x > 0 else 1), ctu + guard * (2 if y > 0 else 1)
+                out.append((0, int(high_res), order, 0, fx, fy, min(fw, W - fx), min(fh, H - fy), x, y, min(ctu, W - x), min(ctu, H - y), 0))
+        for c, (w, h) in enumerate(sizes):
+            out.append((c, int(bool(high_res) and (c == 0 or chroma == "444")), order, 0, 0, 0, w, h, 0, 0, w, h, 0))
+        return np.array(out, VISACT_AREA_DTYPE)
+
+    def visact_picture(self, cur, prev1, prev2, ctu, bit_depth, high_res, order, chroma="420", out=None):
+        """vvhip_visact over the area list of visact_picture_areas.  cur / prev1 / prev2: per component a Plane or PlaneView ([ luma ] or [ luma, cb, cr ]); prev1 / prev2 may be
+        None (order 0 / 1).  -> ( records ( n, 4 ), areas ): the CTUs' records first, then one per component"""
+        n = len(cur)
+        prev1, prev2 = prev1 if prev1 is not None else [None] * n, prev2 if prev2 is not None else [None] * n
+        areas = self.visact_picture_areas([(p.width, p.height) for p in cur], ctu, high_res, order, chroma)
+        return self.visact([(cur[c], prev1[c], prev2[c], bit_depth) for c in range(n)], areas, out), areas
 
     # ---- SURVEY 8f rank 2: MCTF apply side ----
     REF_STRENGTHS = ((0.84375, 0.6, 0.4286, 0.3333, 0.2727, 0.2308), (1.12500, 1.0, 0.7143, 0.5556, 0.4545, 0.3846))      # MCTF.cpp:112-117
