@@ -1086,6 +1086,59 @@ typedef struct
 } vvhip_visact_area;               /* 40 bytes */
 VVHIP_API int vvhip_visact( vvhip_ctx* ctx, const vvhip_visact_plane* planes, int n_planes, const vvhip_visact_area* areas_host, int n, uint64_t* d_out /* [n][4] */ );
 
+/* ======================================================================================================================
+ * Intra luma mode pre-selection: the decision-free loop of IntraSearch::xEstimateLumaRdModeList (EncoderLib/IntraSearch.cpp:171-335) for a LIST of blocks in one call — per
+ * block one set of reference lines, per requested mode the prediction and its DF_HAD_2SAD cost against the original.  Only the costs leave the device, plus the predictions
+ * the caller asks for.
+ *   vvhip_intra_luma_modes_batch <- per requested mode m of an item, bit for bit:
+ *     IntraPrediction::initPredIntraParams (CommonLib/IntraPrediction.cpp:409-496) for a non-ISP, non-MIP, non-BDPCM luma block: getWideAngle (:335-351), the two angle tables,
+ *       applyPDPC and angularScale, refFilterFlag / interpolationFlag from m_aucIntraFilter (:66-76) and isIntegerSlope, planar's w * h > 32 rule, and everything that
+ *       multi_ref_idx != 0 switches off (PDPC, both filters' selection);
+ *     the [1 2 1] reference filter of xFilterReferenceSamples (:994-1030), once per item;
+ *     predIntraAng's dispatch (:353-383): planar (xPredIntraPlanar_Core :79-135), DC (xGetPredValDc :302-333 with its multiRefIndex + 1 offset), IntraPredSampleFilter
+ *       (:137-157) for planar and DC under applyPDPC, and all of xPredIntraAng (:518-681): the negative-angle side projection with absInvAngle, the replication of the main
+ *       reference's end ( maxIndex = ( multiRefIdx << s ) + 2 ), the pure horizontal / vertical copy with and without IntraHorVerPDPC (:159-175), the integer-slope copy, the
+ *       4-tap path (IntraPredAngleLuma :191-223) with the cubic table (InterpolationFilter::getChromaFilterTable; clipped) or the smoothing filter built from deltaFract (not
+ *       clipped), IntraAnglePDPC (:176-189), and the transposition of horizontal modes;
+ *     the cost min( xGetHADs<false>, 2 * SAD >> DISTORTION_PRECISION_ADJUSTMENT ) of RdCost::xGetHAD2SADs (CommonLib/RdCost.cpp:1768-1816) — VVHIP_DF_HAD_2SAD on compact blocks.
+ * The clip range is [0, 2^bit_depth - 1] (the reference's ClpRng).
+ * Reference lines (d_ref + ref_off, int16): the UNFILTERED lines of the block exactly as xFillReferenceSamples (:755-990) leaves m_refBuffer[COMP_Y][PRED_BUF_UNFILTERED] for
+ * the item's multi_ref_idx r, with predStride = 2w + 1 + r:
+ *     [0]                          the corner sample, at ( -1 - r, -1 - r ) of the block
+ *     [1 + k], k < 2w + r          the row above: sample ( -r + k, -1 - r )                         — 2w + 1 + r samples from the corner
+ *     [predStride]                 the corner sample again
+ *     [predStride + 1 + k], k < 2h + r   the column to the left: sample ( -1 - r, -r + k )          — 2h + 1 + r samples from the corner
+ *   ( 2w + 1 + r ) + ( 2h + 1 + r ) samples in all.  Availability and substitution are the caller's: the entry reads every one of them.
+ * Original (d_org + org_off, int16): the block, compact (stride = w), as xGetHAD2SADs assumes.
+ * Costs (d_cost + cost_off, uint32): 67 slots per item, indexed by mode; slot m receives the cost of every mode m of mode_mask, the other slots are not written.
+ * Predictions (d_pred + pred_off, int16): the blocks of the modes of pred_mask, compact, in ascending mode order — popcount( pred_mask ) * w * h samples; nothing beyond them
+ * is written.  d_pred may be NULL when no item has a pred_mask bit.
+ * A mask is 67 bits: mode m is bit ( m & 31 ) of word m >> 5.
+ * An item's results depend on nothing but the item: they are independent of the list's order and identical from run to run (integer arithmetic; the per-mode tile sums are
+ * integer additions, which commute).  Items whose output regions overlap are the caller's error.
+ * items_host is a HOST array, validated and uploaded by the call (the copy a previous launch may still read is waited for first).
+ * VVHIP_E_ARG, before any launch and with nothing written: n < 0; w or h outside { 4, 8, 16, 32, 64 }; bit_depth outside 8..12; multi_ref_idx > 2; PLANAR (mode 0) requested with
+ * multi_ref_idx != 0 (the reference never forms it, IntraSearch.cpp:308); mask bits >= 67; pred_mask not a subset of mode_mask; a negative offset; a non-zero rsv;
+ * d_pred == NULL with a non-empty pred_mask; a missing array with n > 0.  n == 0 succeeds and launches nothing.
+ * Still the caller's (out of scope here): xFillReferenceSamples itself (availability and substitution are syntax-bound); the MPM list, xFracModeBitsIntraLuma, lambda and
+ * updateCandList; the decimated rounds of IntraSearch.cpp:229-292 (a mode's cost does not depend on the round: one call with the full mask serves every round — INTEGRATION.md);
+ * MIP, ISP, BDPCM; chroma, including CCLM; LMCS; hooking the entry into the running encoder.                                                                                   */
+typedef struct
+{
+  uint8_t  w, h;                   /* 4, 8, 16, 32, 64                                                            */
+  uint8_t  bit_depth;              /* 8..12                                                                       */
+  uint8_t  multi_ref_idx;          /* 0, 1, 2: the reference line                                                 */
+  int32_t  ref_off;                /* into d_ref: the unfiltered lines (layout above)                             */
+  int32_t  org_off;                /* into d_org: the original block, compact                                     */
+  int32_t  pred_off;               /* into d_pred: the predictions of pred_mask, ascending modes                  */
+  int32_t  cost_off;               /* into d_cost: 67 slots, indexed by mode                                      */
+  uint32_t mode_mask[3];           /* the modes to score                                                          */
+  uint32_t pred_mask[3];           /* the modes whose prediction is written: a subset of mode_mask                */
+  uint32_t rsv;                    /* 0                                                                           */
+} vvhip_intra_item;                /* 48 bytes */
+VVHIP_API int vvhip_intra_luma_modes_batch( vvhip_ctx* ctx, const vvhip_intra_item* items_host, int n, const int16_t* d_ref, const int16_t* d_org, int16_t* d_pred /* may be NULL */,
+                                            uint32_t* d_cost );
+
 #ifdef __cplusplus
 }
 #endif

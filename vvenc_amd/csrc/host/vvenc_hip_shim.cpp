@@ -1747,6 +1747,83 @@ int VisActOps::avg( int i ) const
 
 VisActOps::~VisActOps() {}      // (device areas are released with the process, like ALFOps')
 
+// ------------------------------------------------------------------------------------------------ IntraOps
+void IntraOps::begin() { m_items.clear(); m_ref.clear(); m_org.clear(); m_pred.clear(); m_cost.clear(); m_ran = false; }
+
+int IntraOps::add( const Pel* refBuf, int refStride, const Pel* piOrg, int orgStride, int width, int height, int bitDepth, int multiRefIdx, const uint8_t* intraDir, int numModes,
+                   const uint8_t* predDir, int numPred )
+{
+  auto sizeOk = []( int v ) { return v == 4 || v == 8 || v == 16 || v == 32 || v == 64; };
+  if( !refBuf || !piOrg || !sizeOk( width ) || !sizeOk( height ) || bitDepth < 8 || bitDepth > 12 || multiRefIdx < 0 || multiRefIdx > 2 || numModes < 0 || numPred < 0 ||
+      ( numModes && !intraDir ) || ( numPred && !predDir ) || refStride < 2 * width + 1 + multiRefIdx || orgStride < width ) return -1;
+  vvhip_intra_item q;
+  memset( &q, 0, sizeof( q ) );
+  for( int k = 0; k < numModes; k++ )
+  {
+    if( intraDir[k] > 66 || ( intraDir[k] == 0 && multiRefIdx ) ) return -1;
+    q.mode_mask[intraDir[k] >> 5] |= 1u << ( intraDir[k] & 31 );
+  }
+  int nPred = 0;
+  for( int k = 0; k < numPred; k++ )
+  {
+    const int m = predDir[k];
+    if( m > 66 || !( ( q.mode_mask[m >> 5] >> ( m & 31 ) ) & 1 ) ) return -1;
+    if( !( ( q.pred_mask[m >> 5] >> ( m & 31 ) ) & 1 ) ) nPred++;
+    q.pred_mask[m >> 5] |= 1u << ( m & 31 );
+  }
+  q.w = ( uint8_t ) width; q.h = ( uint8_t ) height; q.bit_depth = ( uint8_t ) bitDepth; q.multi_ref_idx = ( uint8_t ) multiRefIdx;
+  q.ref_off = ( int32_t ) m_ref.size(); q.org_off = ( int32_t ) m_org.size(); q.pred_off = ( int32_t ) m_pred.size(); q.cost_off = ( int32_t ) ( 67 * m_items.size() );
+  const int nt = 2 * width + 1 + multiRefIdx, nl = 2 * height + 1 + multiRefIdx;
+  m_ref.insert( m_ref.end(), refBuf, refBuf + nt );
+  m_ref.insert( m_ref.end(), refBuf + refStride, refBuf + refStride + nl );
+  for( int y = 0; y < height; y++ ) m_org.insert( m_org.end(), piOrg + ( ptrdiff_t ) y * orgStride, piOrg + ( ptrdiff_t ) y * orgStride + width );
+  m_pred.resize( m_pred.size() + ( size_t ) nPred * width * height );
+  m_items.push_back( q );
+  m_ran = false;
+  return ( int ) m_items.size() - 1;
+}
+
+bool IntraOps::run()
+{
+  if( m_items.empty() ) return false;
+  Device& dev = Device::get();
+  auto pad = []( size_t b ) { return ( b + 255 ) & ~( size_t ) 255; };
+  const size_t refB = pad( m_ref.size() * sizeof( Pel ) ), orgB = pad( m_org.size() * sizeof( Pel ) ), predB = pad( m_pred.size() * sizeof( Pel ) ), costB = pad( m_items.size() * 67 * sizeof( uint32_t ) );
+  const size_t total = refB + orgB + predB + costB;
+  if( m_gpu != dev.gpu() || m_devBytes < total )
+  {
+    if( m_d && m_gpu == dev.gpu() ) vvhip_free( dev.ctx(), m_d );      // (an area of another GPU is released with the process)
+    void* p = nullptr;
+    m_d = nullptr; m_devBytes = 0;
+    dev.check( vvhip_malloc( dev.ctx(), &p, total ), "intra mode list" );
+    m_d = static_cast<char*>( p ); m_devBytes = total; m_gpu = dev.gpu();
+  }
+  int16_t* dRef = reinterpret_cast<int16_t*>( m_d ); int16_t* dOrg = reinterpret_cast<int16_t*>( m_d + refB ); int16_t* dPred = reinterpret_cast<int16_t*>( m_d + refB + orgB );
+  uint32_t* dCost = reinterpret_cast<uint32_t*>( m_d + refB + orgB + predB );
+  dev.check( vvhip_upload( dev.ctx(), dRef, m_ref.data(), m_ref.size() * sizeof( Pel ) ), "intra reference lines" );
+  dev.check( vvhip_upload( dev.ctx(), dOrg, m_org.data(), m_org.size() * sizeof( Pel ) ), "intra originals" );
+  dev.check( vvhip_intra_luma_modes_batch( dev.ctx(), m_items.data(), ( int ) m_items.size(), dRef, dOrg, m_pred.empty() ? nullptr : dPred, dCost ), "vvhip_intra_luma_modes_batch" );
+  m_cost.assign( m_items.size() * 67, 0 );
+  dev.check( vvhip_download( dev.ctx(), m_cost.data(), dCost, m_cost.size() * sizeof( uint32_t ) ), "intra costs" );
+  if( !m_pred.empty() ) dev.check( vvhip_download( dev.ctx(), m_pred.data(), dPred, m_pred.size() * sizeof( Pel ) ), "intra predictions" );
+  // slots of modes that were not scored hold whatever the device area held: make them 0
+  for( size_t i = 0; i < m_items.size(); i++ )
+    for( int m = 0; m < 67; m++ ) if( !scored( ( int ) i, m ) ) m_cost[67 * i + m] = 0;
+  m_ran = true;
+  return true;
+}
+
+const Pel* IntraOps::pred( int i, int intraDir ) const
+{
+  const vvhip_intra_item& q = m_items.at( i );
+  if( !m_ran || intraDir < 0 || intraDir > 66 || !( ( q.pred_mask[intraDir >> 5] >> ( intraDir & 31 ) ) & 1 ) ) return nullptr;
+  int rank = 0;
+  for( int m = 0; m < intraDir; m++ ) rank += ( q.pred_mask[m >> 5] >> ( m & 31 ) ) & 1;
+  return m_pred.data() + q.pred_off + ( size_t ) rank * q.w * q.h;
+}
+
+IntraOps::~IntraOps() {}      // (device areas are released with the process, like ALFOps')
+
 bool ALFOps::getStatisticsCcAlf( const Pel* orgC, int orgStride, const Pel* slfC, int slfStride, const Pel* recLuma, int recStride, int widthC, int heightC, int ctuSizeC,
                                  int vbCTUHeight, int vbPos, int picHeight, float* out, const float* init )
 {

@@ -470,6 +470,36 @@ private:
   std::vector<uint64_t> m_rec;
 };
 
+// Intra luma mode pre-selection (vvhip_intra_luma_modes_batch): the predict-and-score loop of IntraSearch::xEstimateLumaRdModeList (EncoderLib/IntraSearch.cpp:171-335) for a
+// list of blocks — per block the reference lines xFillReferenceSamples left, per mode initPredIntraParams, predIntraAng and DF_HAD_2SAD against the original.  The MPM list,
+// the mode bits, lambda and updateCandList stay with the encoder: it reads the costs (and the predictions it asked for) and decides.
+struct IntraOps
+{
+  // begin empties the list.  add appends one luma block (any thread that later calls run): refBuf is the UNFILTERED reference buffer as
+  // m_refBuffer[COMP_Y][PRED_BUF_UNFILTERED] holds it for multiRefIdx — the top row at refBuf, the left row at refBuf + refStride, refStride >= 2 width + 1 + multiRefIdx
+  // (m_refBufferStride) — piOrg / orgStride the original block (copied compact); intraDir[ numModes ] the modes to score, predDir[ numPred ] those of them whose prediction is
+  // wanted (may be NULL / 0).  -> the block's index, -1 for an argument the entry would refuse on sight (size, bit depth, multiRefIdx, a mode beyond 66, PLANAR with
+  // multiRefIdx != 0, a predDir that is not scored).
+  // run uploads lines and originals, runs the entry on the calling thread's stream and downloads costs and predictions; false: an empty list.
+  void begin();
+  int  add( const Pel* refBuf, int refStride, const Pel* piOrg, int orgStride, int width, int height, int bitDepth, int multiRefIdx, const uint8_t* intraDir, int numModes,
+            const uint8_t* predDir = nullptr, int numPred = 0 );
+  bool run();
+  int  count() const { return ( int ) m_items.size(); }
+  bool scored( int i, int intraDir ) const { const vvhip_intra_item& q = m_items.at( i ); return intraDir >= 0 && intraDir < 67 && ( ( q.mode_mask[intraDir >> 5] >> ( intraDir & 31 ) ) & 1 ); }
+  uint32_t cost( int i, int intraDir ) const { return m_cost.at( ( size_t ) 67 * i + intraDir ); }      // min( HAD, 2 SAD ) of a scored mode (Distortion)
+  const Pel* pred( int i, int intraDir ) const;      // the prediction block, compact (stride = width); NULL where it was not asked for
+  ~IntraOps();
+private:
+  bool m_ran = false;
+  int m_gpu = -1;
+  size_t m_devBytes = 0;
+  char* m_d = nullptr;
+  std::vector<vvhip_intra_item> m_items;
+  std::vector<Pel> m_ref, m_org, m_pred;
+  std::vector<uint32_t> m_cost;
+};
+
 // MCTF table, CommonLib/MCTF.h:160-170
 struct MCTFOps
 {

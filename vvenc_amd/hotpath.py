@@ -110,6 +110,9 @@ LF_PARAM_DTYPE = np.dtype([("qp", "i1", (3,)), ("bs", "u1"), ("side_max_filt_len
 DBK_VER, DBK_HOR = 1, 2      # VVHIP_DBK_*
 VISACT_AREA_DTYPE = np.dtype([("plane", "u1"), ("ds", "u1"), ("order", "u1"), ("rsv0", "u1"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"),
                               ("mx", "<i4"), ("my", "<i4"), ("mw", "<i4"), ("mh", "<i4"), ("rsv1", "<i4")])      # vvhip_visact_area (40 bytes)
+INTRA_ITEM_DTYPE = np.dtype([("w", "u1"), ("h", "u1"), ("bit_depth", "u1"), ("multi_ref_idx", "u1"), ("ref_off", "<i4"), ("org_off", "<i4"), ("pred_off", "<i4"),
+                             ("cost_off", "<i4"), ("mode_mask", "<u4", (3,)), ("pred_mask", "<u4", (3,)), ("rsv", "<u4")])      # vvhip_intra_item (48 bytes)
+INTRA_MODES = 67      # NUM_LUMA_MODE: the cost slots of an item
 SBT_MAX_DIST = (1 << 64) - 1      # MAX_DISTORTION: the estimate of a mode whose type is not allowed
 
 
@@ -867,6 +870,32 @@ class HotPath:
         prev1, prev2 = prev1 if prev1 is not None else [None] * n, prev2 if prev2 is not None else [None] * n
         areas = self.visact_picture_areas([(p.width, p.height) for p in cur], ctu, high_res, order, chroma)
         return self.visact([(cur[c], prev1[c], prev2[c], bit_depth) for c in range(n)], areas, out), areas
+
+    # ---- intra luma mode pre-selection (intra.hip) ----
+    @staticmethod
+    def intra_layout(items):
+        """a copy of the items with cost_off = 67 * i and the predictions packed in list order -> ( items, prediction samples in all )"""
+        it = np.ascontiguousarray(items, INTRA_ITEM_DTYPE).reshape(-1).copy()
+        at = 0
+        for i in range(it.size):
+            it[i]["cost_off"], it[i]["pred_off"] = INTRA_MODES * i, at
+            at += sum(bin(int(m)).count("1") for m in it[i]["pred_mask"]) * int(it[i]["w"]) * int(it[i]["h"])
+        return it, at
+
+    def intra_luma_modes(self, items, ref, org, cost=None, pred=None):
+        """vvhip_intra_luma_modes_batch: every mode of mode_mask of every item predicted from the item's reference lines and scored with HAD_2SAD against its original; the
+        predictions of pred_mask written.  items: INTRA_ITEM_DTYPE [ n ]; ref / org: int16 device tensors (the lines, the compact originals).
+        Without cost / pred the items are laid out by intra_layout and fresh zeroed tensors are returned; with cost ( int32, the uint32 costs ) and pred ( int16, or None where no
+        item asks for predictions ) given, the items' own cost_off / pred_off are used and nothing but the requested slots and blocks is written.
+        -> ( cost viewed as ( -1, 67 ) where it was made here, pred, the items as run )"""
+        it = np.ascontiguousarray(items, INTRA_ITEM_DTYPE).reshape(-1)
+        if cost is None:
+            it, npred = self.intra_layout(it)
+            cost = torch.zeros((it.size, INTRA_MODES), dtype=torch.int32, device=self.device)
+            pred = torch.zeros(npred, dtype=torch.int16, device=self.device) if npred else None
+        assert cost.dtype == torch.int32 and ref.dtype == torch.int16 and org.dtype == torch.int16 and (pred is None or pred.dtype == torch.int16)
+        self._ck(self.L.vvhip_intra_luma_modes_batch(self.ctx, it.ctypes.data_as(C.c_void_p), it.size, _ptr(ref), _ptr(org), _ptr(pred), _ptr(cost)))
+        return cost, pred, it
 
     # ---- SURVEY 8f rank 2: MCTF apply side ----
     REF_STRENGTHS = ((0.84375, 0.6, 0.4286, 0.3333, 0.2727, 0.2308), (1.12500, 1.0, 0.7143, 0.5556, 0.4545, 0.3846))      # MCTF.cpp:112-117
