@@ -1122,7 +1122,7 @@ VVHIP_API int vvhip_visact( vvhip_ctx* ctx, const vvhip_visact_plane* planes, in
  * d_pred == NULL with a non-empty pred_mask; a missing array with n > 0.  n == 0 succeeds and launches nothing.
  * Still the caller's (out of scope here): xFillReferenceSamples itself (availability and substitution are syntax-bound); the MPM list, xFracModeBitsIntraLuma, lambda and
  * updateCandList; the decimated rounds of IntraSearch.cpp:229-292 (a mode's cost does not depend on the round: one call with the full mask serves every round — INTEGRATION.md);
- * MIP, ISP, BDPCM; chroma, including CCLM; LMCS; hooking the entry into the running encoder.                                                                                   */
+ * MIP, ISP, BDPCM; chroma (vvhip_intra_chroma_modes_batch below); LMCS; hooking the entry into the running encoder.                                                           */
 typedef struct
 {
   uint8_t  w, h;                   /* 4, 8, 16, 32, 64                                                            */
@@ -1138,6 +1138,83 @@ typedef struct
 } vvhip_intra_item;                /* 48 bytes */
 VVHIP_API int vvhip_intra_luma_modes_batch( vvhip_ctx* ctx, const vvhip_intra_item* items_host, int n, const int16_t* d_ref, const int16_t* d_org, int16_t* d_pred /* may be NULL */,
                                             uint32_t* d_cost );
+
+/* ======================================================================================================================
+ * Intra chroma mode pre-selection: the decision-free loop of IntraSearch::estIntraPredChromaQT (EncoderLib/IntraSearch.cpp:778-862) for a LIST of 4:2:0 chroma blocks in one
+ * call — per block the Cb and the Cr prediction of up to eight candidate modes, each scored with min( 2 * SAD, HAD ), the two added (:827-843).  Only one cost per candidate
+ * leaves the device, plus the predictions the caller asks for (the survivors are predicted again with the same two functions, :1975-1990).
+ *   vvhip_intra_chroma_modes_batch <- per requested slot s of an item with mode m = cand[s], bit for bit, for Cb and for Cr:
+ *     m in 0..66: IntraPrediction::initPredIntraParams for a chroma block (CommonLib/IntraPrediction.cpp:409-496: getWideAngle, the two angle tables, applyPDPC, angularScale;
+ *       no reference filter and no interpolation flag, :461-468), predIntraAng's planar / DC / IntraPredSampleFilter (:353-383), xPredIntraAng (:518-681) with
+ *       IntraPredAngleChroma_Core (:225-245: ( ( 32 - f ) * p0 + f * p1 + 16 ) >> 5 in 32-bit arithmetic, not clipped), the integer-slope copy, IntraHorVerPDPC (clipped)
+ *       and IntraAnglePDPC;
+ *     m in 67..69 (LM_CHROMA, MDLM_L, MDLM_T): the 4:2:0 branches of loadLMLumaRecPels (:1165-1406: the [1 2 1] row of isFirstRowOfCtu, the five-tap cross of
+ *       sps->verCollocatedChroma, the default six-tap, leftPadding, abovePadding), xGetLMParameters (:1408-1605: the template lengths per mode with the clamps of :1487 and
+ *       :1493 applied HERE to n_above_right / n_left_below, startPos / pickStep, the four picked pairs, the four-comparison sort, the rounded means, floorLog2, DivSigTable,
+ *       add, the iShift < 1 clamp to +-15, diff == 0, and the default b = 1 << ( bit_depth - 1 ) when the mode has no template) and linearTransform( a, iShift, b, clip )
+ *       (Buffer.cpp:253) with the clip range [0, 2^bit_depth - 1].  With sides >= 4 every available template yields four pairs: the cnt == 2 branch (:1544) cannot be
+ *       reached.  The parameters read at most four template positions per mode, so only the inner w x h block and the picked positions are down-sampled.
+ *     the cost: min( 2 * SAD, xGetHADs<false> ) of Cb plus the same of Cr (DF_SAD, DF_HAD on compact blocks).
+ * Scope: 4:2:0, chroma sides of 4, 8, 16, 32, bit depths 8..12.
+ * Reference lines (d_ref + ref_off[c], int16; c = 0 Cb, 1 Cr): the UNFILTERED lines of the component in vvhip_intra_luma_modes_batch's layout with multi_ref_idx 0 — corner,
+ *   2w samples above, corner again, 2h samples to the left: ( 2w + 1 ) + ( 2h + 1 ) samples.  They are also the chroma neighbours xGetLMParameters picks (:1523, :1535).
+ * Originals (d_org + org_off[c], int16): compact (stride = w).
+ * Luma (d_luma + luma_off, int16, pitch luma_stride): the top-left sample of the collocated 2w x 2h area in a plane of RECONSTRUCTED luma.  With ( x, y ) counted from that
+ *   sample, AR = min( n_above_right, h ) and LB = min( n_left_below, w ), the entry reads nothing outside
+ *     the area                 columns 0 .. 2w - 1 of rows 0 .. 2h - 1                                      (any mode >= 67 requested)
+ *       left available           plus column -1 of those rows; without it column 0 stands in (leftPadding)
+ *       verCollocatedChroma      plus row -1 over columns 0 .. 2w - 1 when above is available; without it row 0 stands in (abovePadding)
+ *     above available          columns -1 .. 2w - 1 (LM_CHROMA requested) or -1 .. 2( w + AR ) - 1 (MDLM_T requested) of
+ *       first row of the CTU     row -1
+ *       verCollocatedChroma      rows -3 .. -1   (columns 2i +- 1 only in row -2)
+ *       otherwise                rows -2, -1
+ *                              column -1 only when left is available (leftPadding otherwise: column 0)
+ *     left available           columns -3 .. -1 of rows 0 .. 2h - 1 (LM_CHROMA requested) or 0 .. 2( h + LB ) - 1 (MDLM_L requested);
+ *       verCollocatedChroma      plus row -1 of column -2 when above is available (abovePadding otherwise); the row below a position ( 2j + 1 ) is always read
+ *   and inside these regions only the 2 x 3 or cross neighbourhoods of the positions xGetLMParameters picks.  A list without a mode >= 67 reads no luma: d_luma may be NULL.
+ * Costs (d_cost + cost_off, uint32): 8 slots per item, indexed by candidate slot; slot s receives the cost of every slot of mode_mask, the others are not written.
+ * Predictions (d_pred + pred_off[c], int16): the blocks of the slots of pred_mask, compact, in ascending slot order — popcount( pred_mask ) * w * h samples per component;
+ *   nothing beyond them is written.  d_pred may be NULL when no item has a pred_mask bit.
+ * An item's results depend on nothing but the item: independent of the list's order and identical from run to run (integer arithmetic; tile sums are integer additions).
+ * Items whose output regions overlap are the caller's error.  items_host is a HOST array, validated and uploaded by the call.
+ * VVHIP_E_ARG, before any launch and with nothing written: n < 0; w or h outside { 4, 8, 16, 32 }; bit_depth outside 8..12; a cand value above 69 in any slot, requested or
+ * not; unknown flag bits; an odd n_above_right / n_left_below, one that takes its template beyond 2w / 2h samples ( n_above_right > w, n_left_below > h: the reference's
+ * availability walk cannot produce it, and the component's line ends there ), a non-zero one without its side's flag; pred_mask not a subset of mode_mask; a negative
+ * offset or luma_stride; a non-zero rsv byte; d_luma == NULL with a requested mode >= 67; d_pred == NULL with a pred_mask bit; items / d_ref / d_org / d_cost missing with
+ * n > 0.  n == 0 succeeds and launches nothing.
+ * Still the caller's: initIntraPatternChType / xFillReferenceSamples and the availability walk; the isLMCModeEnabled / lmChromaCheckDisable masks and the list of :810 (they
+ * become mode_mask); the sort, the disable list and the RD loop behind them (vvhip::IntraChromaOps offers the sort); BDPCM; chroma sides of 2 and 64; 4:2:2 and 4:4:4;
+ * LMCS chroma scaling; DM from a MIP luma block (the caller puts PLANAR into the slot).                                                                                        */
+#define VVHIP_ICH_ABOVE           1   /* the row above the block is available (aboveIsAvailable, :1226)                     */
+#define VVHIP_ICH_LEFT            2   /* the column to the left is available (leftIsAvailable, :1222)                       */
+#define VVHIP_ICH_FIRST_ROW       4   /* the collocated luma row is the first row of its CTU (isFirstRowOfCtu, :1241)      */
+#define VVHIP_ICH_VER_COLLOCATED  8   /* sps->verCollocatedChroma                                                           */
+typedef struct
+{
+  uint8_t  w, h;                   /* the chroma size: 4, 8, 16, 32                                               */
+  uint8_t  bit_depth;              /* 8..12                                                                       */
+  uint8_t  flags;                  /* VVHIP_ICH_*                                                                 */
+  uint8_t  n_above_right;          /* avaiAboveRightUnits * 2: chroma samples, even, <= w, 0 without ABOVE        */
+  uint8_t  n_left_below;           /* avaiLeftBelowUnits * 2: chroma samples, even, <= h, 0 without LEFT          */
+  uint8_t  mode_mask;              /* the slots of cand to score                                                  */
+  uint8_t  pred_mask;              /* the slots whose predictions are written: a subset of mode_mask              */
+  uint8_t  cand[8];                /* CU::getIntraChromaCandModes: 0..66 regular (the DM slot carries the mode DM */
+                                   /* resolves to), 67 LM_CHROMA, 68 MDLM_L, 69 MDLM_T                            */
+  int32_t  luma_off;               /* into d_luma: the top-left sample of the collocated 2w x 2h area             */
+  int32_t  luma_stride;            /* the luma plane's pitch in samples                                           */
+  int32_t  ref_off[2];             /* into d_ref: the unfiltered lines of Cb, Cr                                  */
+  int32_t  org_off[2];             /* into d_org: the originals of Cb, Cr, compact                                */
+  int32_t  pred_off[2];            /* into d_pred: the predictions of pred_mask of Cb, Cr, ascending slots        */
+  int32_t  cost_off;               /* into d_cost: 8 slots, indexed by candidate slot                             */
+  uint8_t  rsv[12];                /* 0                                                                           */
+} vvhip_intra_chroma_item;         /* 64 bytes */
+#ifdef __cplusplus
+static_assert( sizeof( vvhip_intra_chroma_item ) == 64, "vvhip_intra_chroma_item is 64 bytes" );
+#else
+_Static_assert( sizeof( vvhip_intra_chroma_item ) == 64, "vvhip_intra_chroma_item is 64 bytes" );
+#endif
+VVHIP_API int vvhip_intra_chroma_modes_batch( vvhip_ctx* ctx, const vvhip_intra_chroma_item* items_host, int n, const int16_t* d_luma /* may be NULL */, const int16_t* d_ref,
+                                              const int16_t* d_org, int16_t* d_pred /* may be NULL */, uint32_t* d_cost );
 
 #ifdef __cplusplus
 }

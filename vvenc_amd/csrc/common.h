@@ -85,7 +85,7 @@ struct vvhip_ctx
   // the per-call host arrays of the SAO entries (sao.hip): [0] the CTU flags of vvhip_sao_stats, [1] the CTU parameters of vvhip_sao_offset — and of the deblocking entry
   // (deblock.hip): [2] the band's loop-filter records of vvhip_deblock — device slot, the host copy the asynchronous upload reads, and the event recorded behind the launch
   // that reads the slot — and of the visual-activity entry (visact.hip): [3] the tile list and area table of vvhip_visact, [4] its per-tile partial records (device only) — and of the intra mode list (intra.hip): [5] the items of
-  // vvhip_intra_luma_modes_batch
+  // vvhip_intra_luma_modes_batch, [6] the items of vvhip_intra_chroma_modes_batch (intrachroma.hip)
   struct SaoSlot
   {
     void*        d         = nullptr;
@@ -93,7 +93,7 @@ struct vvhip_ctx
     std::vector<unsigned char> blob;
     hipEvent_t   event     = nullptr;
     bool         eventRecorded = false;
-  } saoSlot[6];
+  } saoSlot[7];
   // how the host waits for the stream (vvhip_set_blocking_sync): false = hipStreamSynchronize (the runtime's low-latency wait), true = a blocking event — the calling thread
   // sleeps, which matters when the host's cores are all busy encoding
   bool         blockingSync = false;

@@ -1824,6 +1824,124 @@ const Pel* IntraOps::pred( int i, int intraDir ) const
 
 IntraOps::~IntraOps() {}      // (device areas are released with the process, like ALFOps')
 
+// ------------------------------------------------------------------------------------------------ IntraChromaOps
+void IntraChromaOps::begin()
+{
+  m_items.clear(); m_ref.clear(); m_org.clear(); m_pred.clear(); m_cost.clear(); m_ran = false;
+  m_hostLuma = nullptr; m_devLuma = nullptr; m_lumaStride = m_lumaW = m_lumaH = 0;
+}
+
+void IntraChromaOps::setLuma( const Pel* recoLuma, int stride, int width, int height ) { m_hostLuma = recoLuma; m_devLuma = nullptr; m_lumaStride = stride; m_lumaW = width; m_lumaH = height; m_ran = false; }
+void IntraChromaOps::setResidentLuma( const int16_t* dLuma, int stride, int width, int height ) { m_devLuma = dLuma; m_hostLuma = nullptr; m_lumaStride = stride; m_lumaW = width; m_lumaH = height; m_ran = false; }
+
+int IntraChromaOps::add( const Pel* refCb, int refStrideCb, const Pel* refCr, int refStrideCr, const Pel* orgCb, const Pel* orgCr, int orgStride, int lumaX, int lumaY, int width, int height,
+                         int bitDepth, bool aboveAvail, bool leftAvail, int avaiAboveRightUnits, int avaiLeftBelowUnits, bool firstRowOfCtu, bool verCollocatedChroma, const uint8_t cand[8],
+                         unsigned modeMask, unsigned predMask )
+{
+  auto sizeOk = []( int v ) { return v == 4 || v == 8 || v == 16 || v == 32; };
+  if( !refCb || !refCr || !orgCb || !orgCr || !cand || !sizeOk( width ) || !sizeOk( height ) || bitDepth < 8 || bitDepth > 12 || refStrideCb < 2 * width + 1 || refStrideCr < 2 * width + 1 ||
+      orgStride < width || modeMask > 0xff || ( predMask & ~modeMask ) || avaiAboveRightUnits < 0 || avaiLeftBelowUnits < 0 || 2 * avaiAboveRightUnits > width || 2 * avaiLeftBelowUnits > height ||
+      ( avaiAboveRightUnits && !aboveAvail ) || ( avaiLeftBelowUnits && !leftAvail ) || lumaX < 0 || lumaY < 0 ) return -1;
+  bool lm = false, lmT = false, lmL = false;                       // a requested mode >= 67; MDLM_T / MDLM_L among them (the modes that read the extended templates)
+  for( int s = 0; s < 8; s++ )
+  {
+    if( cand[s] > 69 ) return -1;
+    const bool req = ( modeMask >> s ) & 1;
+    lm = lm || ( req && cand[s] >= 67 ); lmL = lmL || ( req && cand[s] == 68 ); lmT = lmT || ( req && cand[s] == 69 );
+  }
+  vvhip_intra_chroma_item q;
+  memset( &q, 0, sizeof( q ) );
+  q.w = ( uint8_t ) width; q.h = ( uint8_t ) height; q.bit_depth = ( uint8_t ) bitDepth;
+  q.flags = ( uint8_t ) ( ( aboveAvail ? VVHIP_ICH_ABOVE : 0 ) | ( leftAvail ? VVHIP_ICH_LEFT : 0 ) | ( firstRowOfCtu ? VVHIP_ICH_FIRST_ROW : 0 ) | ( verCollocatedChroma ? VVHIP_ICH_VER_COLLOCATED : 0 ) );
+  q.n_above_right = ( uint8_t ) ( 2 * avaiAboveRightUnits ); q.n_left_below = ( uint8_t ) ( 2 * avaiLeftBelowUnits );
+  q.mode_mask = ( uint8_t ) modeMask; q.pred_mask = ( uint8_t ) predMask;
+  memcpy( q.cand, cand, 8 );
+  if( lm )
+  {
+    // the footprint of the entry's luma reads (include/vvenc_hip.h) must lie inside the plane
+    if( ( !m_hostLuma && !m_devLuma ) || m_lumaStride < m_lumaW ) return -1;
+    const int rowsAbove = aboveAvail ? ( firstRowOfCtu ? 1 : ( verCollocatedChroma ? 3 : 2 ) ) : 0, colsLeft = leftAvail ? 3 : 0;
+    const int ar = lmT ? std::min( 2 * avaiAboveRightUnits, height ) : 0, lb = lmL ? std::min( 2 * avaiLeftBelowUnits, width ) : 0;
+    if( lumaX - colsLeft < 0 || lumaY - rowsAbove < 0 || lumaX + 2 * ( width + ar ) > m_lumaW || lumaY + 2 * ( height + lb ) > m_lumaH ) return -1;
+    q.luma_off = ( int32_t ) ( ( ptrdiff_t ) lumaY * m_lumaStride + lumaX ); q.luma_stride = m_lumaStride;
+  }
+  const int nPred = __builtin_popcount( predMask ), n = width * height;
+  q.ref_off[0] = ( int32_t ) m_ref.size(); q.ref_off[1] = q.ref_off[0] + 2 * width + 1 + 2 * height + 1;
+  q.org_off[0] = ( int32_t ) m_org.size(); q.org_off[1] = q.org_off[0] + n;
+  q.pred_off[0] = ( int32_t ) m_pred.size(); q.pred_off[1] = q.pred_off[0] + nPred * n;
+  q.cost_off = ( int32_t ) ( 8 * m_items.size() );
+  const Pel* refs[2] = { refCb, refCr }; const int strides[2] = { refStrideCb, refStrideCr }; const Pel* orgs[2] = { orgCb, orgCr };
+  for( int c = 0; c < 2; c++ )
+  {
+    m_ref.insert( m_ref.end(), refs[c], refs[c] + 2 * width + 1 );
+    m_ref.insert( m_ref.end(), refs[c] + strides[c], refs[c] + strides[c] + 2 * height + 1 );
+    for( int y = 0; y < height; y++ ) m_org.insert( m_org.end(), orgs[c] + ( ptrdiff_t ) y * orgStride, orgs[c] + ( ptrdiff_t ) y * orgStride + width );
+  }
+  m_pred.resize( m_pred.size() + ( size_t ) 2 * nPred * n );
+  m_items.push_back( q );
+  m_ran = false;
+  return ( int ) m_items.size() - 1;
+}
+
+bool IntraChromaOps::run()
+{
+  if( m_items.empty() ) return false;
+  Device& dev = Device::get();
+  auto pad = []( size_t b ) { return ( b + 255 ) & ~( size_t ) 255; };
+  bool lm = false;                                                  // the luma plane travels only when an item reads it
+  for( const vvhip_intra_chroma_item& q : m_items ) lm = lm || q.luma_stride != 0;
+  const bool upLuma = lm && m_hostLuma;
+  const size_t lumaB = upLuma ? pad( ( size_t ) m_lumaStride * m_lumaH * sizeof( Pel ) ) : 0;
+  const size_t refB = pad( m_ref.size() * sizeof( Pel ) ), orgB = pad( m_org.size() * sizeof( Pel ) ), predB = pad( m_pred.size() * sizeof( Pel ) ), costB = pad( m_items.size() * 8 * sizeof( uint32_t ) );
+  const size_t total = lumaB + refB + orgB + predB + costB;
+  if( m_gpu != dev.gpu() || m_devBytes < total )
+  {
+    if( m_d && m_gpu == dev.gpu() ) vvhip_free( dev.ctx(), m_d );      // (an area of another GPU is released with the process)
+    void* p = nullptr;
+    m_d = nullptr; m_devBytes = 0;
+    dev.check( vvhip_malloc( dev.ctx(), &p, total ), "intra chroma mode list" );
+    m_d = static_cast<char*>( p ); m_devBytes = total; m_gpu = dev.gpu();
+  }
+  int16_t* dLumaUp = reinterpret_cast<int16_t*>( m_d ); int16_t* dRef = reinterpret_cast<int16_t*>( m_d + lumaB ); int16_t* dOrg = reinterpret_cast<int16_t*>( m_d + lumaB + refB );
+  int16_t* dPred = reinterpret_cast<int16_t*>( m_d + lumaB + refB + orgB );
+  uint32_t* dCost = reinterpret_cast<uint32_t*>( m_d + lumaB + refB + orgB + predB );
+  if( upLuma ) dev.check( vvhip_upload( dev.ctx(), dLumaUp, m_hostLuma, ( size_t ) m_lumaStride * m_lumaH * sizeof( Pel ) ), "intra chroma luma plane" );
+  dev.check( vvhip_upload( dev.ctx(), dRef, m_ref.data(), m_ref.size() * sizeof( Pel ) ), "intra chroma reference lines" );
+  dev.check( vvhip_upload( dev.ctx(), dOrg, m_org.data(), m_org.size() * sizeof( Pel ) ), "intra chroma originals" );
+  const int16_t* dLuma = upLuma ? dLumaUp : ( lm ? m_devLuma : nullptr );
+  dev.check( vvhip_intra_chroma_modes_batch( dev.ctx(), m_items.data(), ( int ) m_items.size(), dLuma, dRef, dOrg, m_pred.empty() ? nullptr : dPred, dCost ), "vvhip_intra_chroma_modes_batch" );
+  m_cost.assign( m_items.size() * 8, 0 );
+  dev.check( vvhip_download( dev.ctx(), m_cost.data(), dCost, m_cost.size() * sizeof( uint32_t ) ), "intra chroma costs" );
+  if( !m_pred.empty() ) dev.check( vvhip_download( dev.ctx(), m_pred.data(), dPred, m_pred.size() * sizeof( Pel ) ), "intra chroma predictions" );
+  // slots that were not scored hold whatever the device area held: they keep cost 0, as satdSortedCost does for the modes IntraSearch.cpp:806-813 skips
+  for( size_t i = 0; i < m_items.size(); i++ )
+    for( int s = 0; s < 8; s++ ) if( !scored( ( int ) i, s ) ) m_cost[8 * i + s] = 0;
+  m_ran = true;
+  return true;
+}
+
+const Pel* IntraChromaOps::pred( int i, int comp, int slot ) const
+{
+  const vvhip_intra_chroma_item& q = m_items.at( i );
+  if( !m_ran || comp < 0 || comp > 1 || slot < 0 || slot > 7 || !( ( q.pred_mask >> slot ) & 1 ) ) return nullptr;
+  const int rank = __builtin_popcount( q.pred_mask & ( ( 1u << slot ) - 1 ) );
+  return m_pred.data() + q.pred_off[comp] + ( size_t ) rank * q.w * q.h;
+}
+
+void IntraChromaOps::select( const uint32_t cost[8], const uint8_t cand[8], bool reduceIntraChromaModesFullRD, uint8_t sortedModes[8], bool disabled[70] )
+{
+  int64_t c[8];
+  for( int s = 0; s < 8; s++ ) { sortedModes[s] = cand[s]; c[s] = cost[s]; }
+  for( int i = 0; i < 8; i++ )
+    for( int j = i + 1; j < 8; j++ )
+      if( c[j] < c[i] ) { std::swap( sortedModes[i], sortedModes[j] ); std::swap( c[i], c[j] ); }
+  for( int m = 0; m < 70; m++ ) disabled[m] = false;
+  const int reducedModeNumber = 8 >> ( reduceIntraChromaModesFullRD ? 1 : 2 );
+  for( int i = 0; i < reducedModeNumber; i++ ) disabled[sortedModes[8 - 1 - i]] = true;
+}
+
+IntraChromaOps::~IntraChromaOps() {}      // (device areas are released with the process, like ALFOps')
+
 bool ALFOps::getStatisticsCcAlf( const Pel* orgC, int orgStride, const Pel* slfC, int slfStride, const Pel* recLuma, int recStride, int widthC, int heightC, int ctuSizeC,
                                  int vbCTUHeight, int vbPos, int picHeight, float* out, const float* init )
 {

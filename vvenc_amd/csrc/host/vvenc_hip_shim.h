@@ -500,6 +500,52 @@ private:
   std::vector<uint32_t> m_cost;
 };
 
+// Intra chroma mode pre-selection (vvhip_intra_chroma_modes_batch): the predict-and-score loop of IntraSearch::estIntraPredChromaQT (EncoderLib/IntraSearch.cpp:778-862) for a
+// list of 4:2:0 chroma blocks — per block the Cb and the Cr prediction of the candidate modes (regular modes from the components' reference lines, CCLM / MDLM from the
+// reconstructed luma) and satdSortedCost.  Availability, the candidate list, the LM masks and everything behind the sort stay with the encoder; select() restates the sort and
+// the disable list for it.
+struct IntraChromaOps
+{
+  // begin empties the list and forgets the luma plane.  The luma plane of the list is EITHER a host plane (setLuma: recoLuma points at sample ( 0, 0 ) of a width x height
+  // picture of reconstructed luma with line pitch stride; uploaded by run) OR a plane that is resident on the device (setResidentLuma: a device pointer at sample ( 0, 0 ),
+  // e.g. the reconstruction DeblockOps / SaoOps / ALFOps keep resident; nothing is uploaded).  A list without a mode >= 67 needs neither.
+  // add appends one chroma block (any thread that later calls run): refCb / refCr are the UNFILTERED reference buffers of the two components as
+  // m_refBuffer[compID][PRED_BUF_UNFILTERED] holds them — the top row at ref, the left row at ref + refStride, refStride >= 2 width + 1 (m_refBufferStride[compID]) —
+  // orgCb / orgCr the original blocks at the picture pitch orgStride (copied compact), ( lumaX, lumaY ) the luma position of the block (chromaArea.lumaPos()), width x height
+  // the chroma size.  aboveAvail / leftAvail / avaiAboveRightUnits / avaiLeftBelowUnits are loadLMLumaRecPels' four availability numbers (units of two chroma samples, NOT yet
+  // clamped: the device applies xGetLMParameters' clamps), firstRowOfCtu and verCollocatedChroma its two other inputs.  cand[8] is CU::getIntraChromaCandModes with the DM slot
+  // resolved (getFinalIntraMode; PLANAR for a MIP luma block); modeMask the slots to score (bit s = slot s: what :806-813 does not skip), predMask those whose predictions
+  // are wanted.  -> the block's index, -1 for an argument the entry would refuse on sight or a block whose luma footprint leaves the plane.
+  // run uploads what the list needs, runs the entry on the calling thread's stream and downloads costs and predictions; false: an empty list.
+  void begin();
+  void setLuma( const Pel* recoLuma, int stride, int width, int height );
+  void setResidentLuma( const int16_t* dLuma, int stride, int width, int height );
+  int  add( const Pel* refCb, int refStrideCb, const Pel* refCr, int refStrideCr, const Pel* orgCb, const Pel* orgCr, int orgStride, int lumaX, int lumaY, int width, int height,
+            int bitDepth, bool aboveAvail, bool leftAvail, int avaiAboveRightUnits, int avaiLeftBelowUnits, bool firstRowOfCtu, bool verCollocatedChroma, const uint8_t cand[8],
+            unsigned modeMask, unsigned predMask = 0 );
+  bool run();
+  int  count() const { return ( int ) m_items.size(); }
+  bool scored( int i, int slot ) const { return slot >= 0 && slot < 8 && ( ( m_items.at( i ).mode_mask >> slot ) & 1 ); }
+  uint32_t cost( int i, int slot ) const { return m_cost.at( ( size_t ) 8 * i + slot ); }      // satdSortedCost of a scored slot; 0 for a slot that was skipped, as in the reference
+  const Pel* pred( int i, int comp, int slot ) const;      // comp 0 Cb, 1 Cr: the prediction block, compact (stride = width); NULL where it was not asked for
+  // the reference's selection from eight costs: the stable exchange sort of IntraSearch.cpp:847-857 over all eight slots (skipped slots carry cost 0) and the disable list of
+  // :859-862 — the last NUM_CHROMA_MODE >> ( reduceIntraChromaModesFullRD ? 1 : 2 ) modes of the sorted list.  sortedModes[8] receives satdModeList after the sort,
+  // disabled[70] is indexed by mode ( modeDisable ).  Host arithmetic only: needs no device.
+  static void select( const uint32_t cost[8], const uint8_t cand[8], bool reduceIntraChromaModesFullRD, uint8_t sortedModes[8], bool disabled[70] );
+  void select( int i, bool reduceIntraChromaModesFullRD, uint8_t sortedModes[8], bool disabled[70] ) const { select( &m_cost.at( ( size_t ) 8 * i ), m_items.at( i ).cand, reduceIntraChromaModesFullRD, sortedModes, disabled ); }
+  ~IntraChromaOps();
+private:
+  bool m_ran = false;
+  int m_gpu = -1;
+  size_t m_devBytes = 0;
+  char* m_d = nullptr;
+  const Pel* m_hostLuma = nullptr; const int16_t* m_devLuma = nullptr;
+  int m_lumaStride = 0, m_lumaW = 0, m_lumaH = 0;
+  std::vector<vvhip_intra_chroma_item> m_items;
+  std::vector<Pel> m_ref, m_org, m_pred;
+  std::vector<uint32_t> m_cost;
+};
+
 // MCTF table, CommonLib/MCTF.h:160-170
 struct MCTFOps
 {

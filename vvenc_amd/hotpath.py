@@ -113,6 +113,11 @@ VISACT_AREA_DTYPE = np.dtype([("plane", "u1"), ("ds", "u1"), ("order", "u1"), ("
 INTRA_ITEM_DTYPE = np.dtype([("w", "u1"), ("h", "u1"), ("bit_depth", "u1"), ("multi_ref_idx", "u1"), ("ref_off", "<i4"), ("org_off", "<i4"), ("pred_off", "<i4"),
                              ("cost_off", "<i4"), ("mode_mask", "<u4", (3,)), ("pred_mask", "<u4", (3,)), ("rsv", "<u4")])      # vvhip_intra_item (48 bytes)
 INTRA_MODES = 67      # NUM_LUMA_MODE: the cost slots of an item
+INTRA_CHROMA_ITEM_DTYPE = np.dtype([("w", "u1"), ("h", "u1"), ("bit_depth", "u1"), ("flags", "u1"), ("n_above_right", "u1"), ("n_left_below", "u1"), ("mode_mask", "u1"),
+                                    ("pred_mask", "u1"), ("cand", "u1", 8), ("luma_off", "<i4"), ("luma_stride", "<i4"), ("ref_off", "<i4", 2), ("org_off", "<i4", 2),
+                                    ("pred_off", "<i4", 2), ("cost_off", "<i4"), ("rsv", "u1", 12)])      # vvhip_intra_chroma_item (64 bytes)
+INTRA_CHROMA_SLOTS = 8      # NUM_CHROMA_MODE: the candidate and cost slots of an item
+ICH_ABOVE, ICH_LEFT, ICH_FIRST_ROW, ICH_VER_COLLOCATED = 1, 2, 4, 8
 SBT_MAX_DIST = (1 << 64) - 1      # MAX_DISTORTION: the estimate of a mode whose type is not allowed
 
 
@@ -895,6 +900,34 @@ class HotPath:
             pred = torch.zeros(npred, dtype=torch.int16, device=self.device) if npred else None
         assert cost.dtype == torch.int32 and ref.dtype == torch.int16 and org.dtype == torch.int16 and (pred is None or pred.dtype == torch.int16)
         self._ck(self.L.vvhip_intra_luma_modes_batch(self.ctx, it.ctypes.data_as(C.c_void_p), it.size, _ptr(ref), _ptr(org), _ptr(pred), _ptr(cost)))
+        return cost, pred, it
+
+    # ---- intra chroma mode pre-selection (intrachroma.hip) ----
+    @staticmethod
+    def intra_chroma_layout(items):
+        """a copy of the items with cost_off = 8 * i and the predictions packed in list order, Cb before Cr per item -> ( items, prediction samples in all )"""
+        it = np.ascontiguousarray(items, INTRA_CHROMA_ITEM_DTYPE).reshape(-1).copy()
+        at = 0
+        for i in range(it.size):
+            n = bin(int(it[i]["pred_mask"])).count("1") * int(it[i]["w"]) * int(it[i]["h"])
+            it[i]["cost_off"], it[i]["pred_off"] = INTRA_CHROMA_SLOTS * i, (at, at + n)
+            at += 2 * n
+        return it, at
+
+    def intra_chroma_modes(self, items, luma, ref, org, cost=None, pred=None):
+        """vvhip_intra_chroma_modes_batch: the Cb and the Cr prediction of every slot of mode_mask of every item — regular modes from the components' reference lines, modes
+        67..69 from the reconstructed luma plane — scored with min( 2 SAD, HAD ) per component and added; the predictions of pred_mask written.  items:
+        INTRA_CHROMA_ITEM_DTYPE [ n ]; luma / ref / org: int16 device tensors (luma may be None when no item asks for a mode >= 67).
+        Without cost / pred the items are laid out by intra_chroma_layout and fresh zeroed tensors are returned; with cost ( int32, the uint32 costs ) and pred ( int16, or None
+        where no item asks for predictions ) given, the items' own cost_off / pred_off are used and nothing but the requested slots and blocks is written.
+        -> ( cost viewed as ( -1, 8 ) where it was made here, pred, the items as run )"""
+        it = np.ascontiguousarray(items, INTRA_CHROMA_ITEM_DTYPE).reshape(-1)
+        if cost is None:
+            it, npred = self.intra_chroma_layout(it)
+            cost = torch.zeros((it.size, INTRA_CHROMA_SLOTS), dtype=torch.int32, device=self.device)
+            pred = torch.zeros(npred, dtype=torch.int16, device=self.device) if npred else None
+        assert cost.dtype == torch.int32 and ref.dtype == torch.int16 and org.dtype == torch.int16 and (pred is None or pred.dtype == torch.int16) and (luma is None or luma.dtype == torch.int16)
+        self._ck(self.L.vvhip_intra_chroma_modes_batch(self.ctx, it.ctypes.data_as(C.c_void_p), it.size, _ptr(luma), _ptr(ref), _ptr(org), _ptr(pred), _ptr(cost)))
         return cost, pred, it
 
     # ---- SURVEY 8f rank 2: MCTF apply side ----
