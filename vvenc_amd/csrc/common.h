@@ -7,6 +7,57 @@
 #include <vector>
 #include "../../include/vvenc_hip.h"
 
+// ---- host lists on the device -------------------------------------------------------------------------------------------------
+// An entry that launches from a host-built array (a sorted schedule, a picture's CTU parameters, a list of items) keeps it in a slot of the context: the device copy, the host
+// copy the asynchronous upload reads, and the event recorded behind the last launch that read the device copy.  A cached entry also stores the key of the caller's list the
+// array was derived from — a list that is run again is neither sorted nor uploaded again; a per-call entry uploads every time and leaves the key empty.  Every use has a slot of
+// its own (ListSlot), so entries that alternate on one context evict nothing of each other's.  What an entry needs to know of its array beside the device pointer (section
+// offsets, unit counts) it puts into a header struct of its own at the front of the blob and reads back through listHead: the host copy is valid exactly as long as the device
+// copy is, and nothing here knows any entry's layout.  The three operations are in ctx.hip: listCurrent, listUpload, listLaunched.
+struct HostList
+{
+  void*        d         = nullptr;      // device copy
+  size_t       bytes     = 0;            // its capacity (grow-only)
+  std::vector<unsigned char> blob;       // host copy: the source of the asynchronous upload, rewritten only after the last reader's event has been waited for
+  std::vector<unsigned char> key;        // the caller's list the copies belong to; empty: none (a per-call array, or an upload that failed)
+  hipStream_t  stream    = nullptr;      // the stream the array was uploaded on; compared only, never used as a handle
+  hipEvent_t   event     = nullptr;      // recorded behind every launch that reads the device copy
+  bool         eventRecorded = false;
+};
+enum ListSlot
+{
+  LIST_PRED, LIST_PRED_BLEND, LIST_PRED_CIIP,      // pred.hip: vvhip_pred_inter_batch[_ex]; ..._blend called with a blend array; ..._ciip called with a CIIP array
+  LIST_AFFINE,                                     // predaffine.hip: vvhip_pred_affine_batch
+  LIST_ICT_FWD, LIST_ICT_INV,                      // ict.hip: vvhip_ict_fwd_batch, vvhip_ict_inv_batch
+  LIST_SBT_PARTS, LIST_SBT_PLACE,                  // sbt.hip: vvhip_sbt_parts_batch, vvhip_sbt_place_batch
+  LIST_SAO_FLAGS, LIST_SAO_PARAMS,                 // sao.hip, per call: the CTU flags of vvhip_sao_stats, the CTU parameters of vvhip_sao_offset
+  LIST_DEBLOCK,                                    // deblock.hip, per call: the band's loop-filter records of vvhip_deblock
+  LIST_VISACT, LIST_VISACT_PART,                   // visact.hip, per call: the tile list and area table of vvhip_visact; its per-tile partial records (device only, see there)
+  LIST_INTRA, LIST_INTRA_CHROMA,                   // intra.hip, intrachroma.hip, per call: the items of vvhip_intra_luma_modes_batch, of vvhip_intra_chroma_modes_batch
+  LIST_COUNT
+};
+
+// the sections of a blob in the order they are added, each starting at a multiple of `align` bytes; the data is copied when the blob is uploaded, so it must live until then
+struct ListBlob
+{
+  struct Sec { const void* data; size_t bytes, off; } sec[8];
+  int          n         = 0;
+  size_t       size      = 0;
+  ListBlob() {}
+  ListBlob( const void* data, size_t bytes ) { add( data, bytes ); }      // a blob of one section
+  size_t add( const void* data, size_t bytes, size_t align = 256 )      // -> the section's offset
+  {
+    size = ( size + align - 1 ) / align * align;
+    sec[n++] = Sec{ data, bytes, size };
+    size += bytes;
+    return sec[n - 1].off;
+  }
+};
+
+// sort key of a list item: size class, position inside the class, list index — a schedule holds the items in this order
+struct ListKeyed { uint32_t cls; int64_t pos; int idx; };
+inline bool operator<( const ListKeyed& a, const ListKeyed& b ) { return a.cls != b.cls ? a.cls < b.cls : a.pos != b.pos ? a.pos < b.pos : a.idx < b.idx; }
+
 struct vvhip_ctx
 {
   int          device     = 0;
@@ -40,60 +91,8 @@ struct vvhip_ctx
   hipStream_t  tuGenStream = nullptr;      // the stream the cached generic-TU job table was uploaded on (trquant.hip: tuRdoMulti); compared only, never used as a handle
   hipEvent_t   tuGenEvent  = nullptr;      // recorded behind every launch that reads the table: a caller that switches streams orders the new stream behind it
   bool         tuGenEventRecorded = false;
-  // device copy of the schedule of vvhip_pred_inter_batch (pred.hip), the caller's list it was derived from (items + plane table: a list that is run again is neither sorted
-  // nor uploaded again) and the host copy the asynchronous upload reads.  [0]: vvhip_pred_inter_batch[_ex]; [1]: vvhip_pred_inter_batch_blend called with a blend array;
-  // [2]: vvhip_pred_inter_batch_ciip called with a CIIP array — each a schedule, key, host copy and event of its own, so that alternating the entries on one context evicts none
-  struct PredSched
-  {
-    void*        d_sched   = nullptr;
-    size_t       bytes     = 0;
-    std::vector<unsigned char> key, blob;
-    size_t       offSubs   = 0, offUnits = 0, offBlend = 0, offCiip = 0;
-    int          units     = 0, ldsPerWave = 0;
-    int          unitsEx   = 0, ldsPerWaveEx = 0;          // the units of items with an extension (BDOF, DMVR's padded reference): behind the plain units, a kernel of their own
-    int          unitsBlend = 0, ldsPerWaveBlend = 0;      // the units of BCW / GEO items: behind those, a kernel of their own; their records sit at offBlend
-    int          unitsCiip = 0, ldsPerWaveCiip = 0;        // the units of CIIP items: behind those, a kernel of their own; their records sit at offCiip
-    hipStream_t  stream    = nullptr;      // the stream the schedule was uploaded on; compared only, never used as a handle
-    hipEvent_t   event     = nullptr;      // recorded behind every launch that reads the schedule
-    bool         eventRecorded = false;
-  } predSched[3];
-  // the same for vvhip_pred_affine_batch (predaffine.hip): a schedule, key, host copy and event of its own — alternating the two entries on one context evicts neither
-  void*        d_affSched = nullptr;
-  size_t       affBytes   = 0;
-  std::vector<unsigned char> affKey, affBlob;
-  size_t       affOffSubs = 0, affOffUnits = 0;
-  int          affUnits   = 0;
-  hipStream_t  affStream  = nullptr;
-  hipEvent_t   affEvent   = nullptr;
-  bool         affEventRecorded = false;
-  // the same for the joint Cb-Cr entries (ict.hip): [0] vvhip_ict_fwd_batch, [1] vvhip_ict_inv_batch — each a schedule (sorted items + wave units), key, host copy and event
-  // of its own, apart from the prediction entries' slots: alternating with them on one context evicts nothing
-  struct IctSched
-  {
-    void*        d_sched   = nullptr;
-    size_t       bytes     = 0;
-    std::vector<unsigned char> key, blob;
-    size_t       offUnits  = 0;
-    int          units     = 0;
-    hipStream_t  stream    = nullptr;      // the stream the schedule was uploaded on; compared only, never used as a handle
-    hipEvent_t   event     = nullptr;      // recorded behind every launch that reads the schedule
-    bool         eventRecorded = false;
-  } ictSched[2];
-  // the same for the sub-block transform entries (sbt.hip): [0] vvhip_sbt_parts_batch, [1] vvhip_sbt_place_batch — slots of their own again, so that alternating them with the
-  // joint Cb-Cr and the prediction entries on one context evicts none of theirs
-  IctSched sbtSched[2];
-  // the per-call host arrays of the SAO entries (sao.hip): [0] the CTU flags of vvhip_sao_stats, [1] the CTU parameters of vvhip_sao_offset — and of the deblocking entry
-  // (deblock.hip): [2] the band's loop-filter records of vvhip_deblock — device slot, the host copy the asynchronous upload reads, and the event recorded behind the launch
-  // that reads the slot — and of the visual-activity entry (visact.hip): [3] the tile list and area table of vvhip_visact, [4] its per-tile partial records (device only) — and of the intra mode list (intra.hip): [5] the items of
-  // vvhip_intra_luma_modes_batch, [6] the items of vvhip_intra_chroma_modes_batch (intrachroma.hip)
-  struct SaoSlot
-  {
-    void*        d         = nullptr;
-    size_t       bytes     = 0;
-    std::vector<unsigned char> blob;
-    hipEvent_t   event     = nullptr;
-    bool         eventRecorded = false;
-  } saoSlot[7];
+  // the host-built arrays the list entries keep on the device, one slot per use (HostList above)
+  HostList     list[LIST_COUNT];
   // how the host waits for the stream (vvhip_set_blocking_sync): false = hipStreamSynchronize (the runtime's low-latency wait), true = a blocking event — the calling thread
   // sleeps, which matters when the host's cores are all busy encoding
   bool         blockingSync = false;
@@ -111,9 +110,18 @@ inline hipError_t vvhip_wait_stream( vvhip_ctx* ctx )
 
 int vvhip_fail( vvhip_ctx* ctx, int code, const char* fmt, ... );
 
-// sao.hip: a per-call host array -> a context slot (waits for the last launch that read the slot, then uploads asynchronously), and the mark behind the launch that reads it
-int saoUpload( vvhip_ctx* ctx, vvhip_ctx::SaoSlot& S, const void* data, size_t bytes );
-int saoMark( vvhip_ctx* ctx, vvhip_ctx::SaoSlot& S );
+// ---- the three operations on a host-list slot (ctx.hip); an entry validates its list BEFORE it calls listUpload, so that a list that fails validation leaves the slot untouched
+// -> *current: the slot holds the list named by `key`, ordered in front of the next launch on the context's stream
+int listCurrent( vvhip_ctx* ctx, HostList& S, const std::vector<unsigned char>& key, bool* current );
+// the blob -> the slot's host copy -> its device copy, asynchronously on the context's stream, after the last launch that read the slot; key: swapped in on success (cached
+// entries), or null for a per-call array, which is never current
+int listUpload( vvhip_ctx* ctx, HostList& S, const ListBlob& blob, std::vector<unsigned char>* key = nullptr );
+// behind the launches that read the slot
+int listLaunched( vvhip_ctx* ctx, HostList& S );
+// the slot's device buffer holds at least `bytes` (grow-only, contents lost on growth); the caller has waited for the slot's readers (listUpload has)
+int listReserve( vvhip_ctx* ctx, HostList& S, size_t bytes );
+// the header struct an entry put at the front of its blob
+template<class H> inline const H& listHead( const HostList& S ) { return *reinterpret_cast<const H*>( S.blob.data() ); }
 
 #define VVHIP_CHECK_HIP( ctx, expr )                                                        \
   do { hipError_t e_ = ( expr );                                                            \

@@ -25,6 +25,73 @@ int vvhip_fail( vvhip_ctx* ctx, int code, const char* fmt, ... )
   return code;
 }
 
+// ---- host lists on the device (common.h: HostList) ---------------------------------------------
+// Slots are per entry: nothing here is shared between entries that can alternate on one context.
+//
+// The slot's stored stream is compared, never dereferenced or synchronised: it may be a borrowed handle (vvhip_set_stream) that no longer exists.  Ordering between streams goes
+// through the event only — here, where a list that is current is run on another stream than the one it was uploaded on: the new stream waits for the event (the upload lies in
+// front of the launch the event was recorded behind) and is adopted.  A list that is current costs nothing else: no allocation, no copy, no host wait, so the entry's call is
+// launches only and can be recorded into a launch graph.
+int listCurrent( vvhip_ctx* ctx, HostList& S, const std::vector<unsigned char>& key, bool* current )
+{
+  *current = !key.empty() && key == S.key;
+  if( *current && S.stream != ctx->stream )
+  {
+    if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipStreamWaitEvent( ctx->stream, S.event, 0 ) );
+    S.stream = ctx->stream;
+  }
+  return VVHIP_OK;
+}
+
+int listReserve( vvhip_ctx* ctx, HostList& S, size_t bytes )
+{
+  if( bytes <= S.bytes ) return VVHIP_OK;
+  if( S.d ) ( void ) hipFree( S.d );
+  S.d = nullptr; S.bytes = 0;
+  const size_t want = bytes + bytes / 4 + 256;
+  VVHIP_CHECK_HIP( ctx, hipMalloc( &S.d, want ) );
+  S.bytes = want;
+  return VVHIP_OK;
+}
+
+// The host copy that hipMemcpyAsync reads is owned by the slot and stays alive behind the call; it and the device copy are rewritten only after the event of the last launch
+// that read the slot has been waited for ON THE HOST, whatever stream that launch went to.  The key is cleared before the slot is touched and installed after the last call
+// that can fail: a failed upload leaves a slot that is never current.
+int listUpload( vvhip_ctx* ctx, HostList& S, const ListBlob& blob, std::vector<unsigned char>* key )
+{
+  if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipEventSynchronize( S.event ) );
+  S.key.clear();
+  const int rc = listReserve( ctx, S, blob.size );
+  if( rc != VVHIP_OK ) return rc;
+  if( blob.size > S.blob.capacity() ) S.blob.clear();      // (nothing of the old copy is worth moving to a larger one)
+  S.blob.resize( blob.size );
+  size_t at = 0;
+  for( int i = 0; i < blob.n; i++ )      // the sections, zeros in the gaps that align them
+  {
+    const ListBlob::Sec& s = blob.sec[i];
+    memset( S.blob.data() + at, 0, s.off - at );
+    if( s.bytes ) memcpy( S.blob.data() + s.off, s.data, s.bytes );
+    at = s.off + s.bytes;
+  }
+  VVHIP_CHECK_HIP( ctx, hipMemcpyAsync( S.d, S.blob.data(), S.blob.size(), hipMemcpyHostToDevice, ctx->stream ) );
+  S.stream = ctx->stream;
+  if( key ) S.key.swap( *key );
+  return VVHIP_OK;
+}
+
+// While the stream is capturing nothing is recorded (and nothing is waited for: a list recorded into a graph is current).  Such a launch runs later: the graph's owner keeps
+// the list unchanged while the graph is in use.
+int listLaunched( vvhip_ctx* ctx, HostList& S )
+{
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if( hipStreamIsCapturing( ctx->stream, &cap ) != hipSuccess ) cap = hipStreamCaptureStatusNone;
+  if( cap != hipStreamCaptureStatusNone ) return VVHIP_OK;
+  if( !S.event ) VVHIP_CHECK_HIP( ctx, hipEventCreateWithFlags( &S.event, hipEventDisableTiming ) );
+  VVHIP_CHECK_HIP( ctx, hipEventRecord( S.event, ctx->stream ) );
+  S.eventRecorded = true;
+  return VVHIP_OK;
+}
+
 // ---- transform matrices ----------------------------------------------------------------------
 // One coefficient per distinct angle (H.266 8.7.4.2): DCT-2 via m = (2n+1)k folded to [0,64];
 // DST-7 via j = (2k+1)(n+1) folded to [0,N]; DCT-8[k][n] = (-1)^k DST-7[k][N-1-n].
@@ -250,28 +317,11 @@ void vvhip_destroy( vvhip_ctx* ctx )
   if( ctx->d_tuGen ) ( void ) hipFree( ctx->d_tuGen );
   if( ctx->syncEvent ) ( void ) hipEventDestroy( ctx->syncEvent );
   if( ctx->tuGenEvent ) ( void ) hipEventDestroy( ctx->tuGenEvent );
-  for( vvhip_ctx::PredSched& S : ctx->predSched )
-  {
-    if( S.d_sched ) ( void ) hipFree( S.d_sched );
-    if( S.event ) ( void ) hipEventDestroy( S.event );
-  }
-  for( vvhip_ctx::IctSched& S : ctx->ictSched )
-  {
-    if( S.d_sched ) ( void ) hipFree( S.d_sched );
-    if( S.event ) ( void ) hipEventDestroy( S.event );
-  }
-  for( vvhip_ctx::IctSched& S : ctx->sbtSched )
-  {
-    if( S.d_sched ) ( void ) hipFree( S.d_sched );
-    if( S.event ) ( void ) hipEventDestroy( S.event );
-  }
-  for( vvhip_ctx::SaoSlot& S : ctx->saoSlot )
+  for( HostList& S : ctx->list )
   {
     if( S.d ) ( void ) hipFree( S.d );
     if( S.event ) ( void ) hipEventDestroy( S.event );
   }
-  if( ctx->d_affSched ) ( void ) hipFree( ctx->d_affSched );
-  if( ctx->affEvent ) ( void ) hipEventDestroy( ctx->affEvent );
   if( ctx->d_mctfStats ) ( void ) hipFree( ctx->d_mctfStats );
   for( hipEvent_t e : ctx->mctfEv ) ( void ) hipEventDestroy( e );
   if( ctx->ownStream ) ( void ) hipStreamDestroy( ctx->ownStream );

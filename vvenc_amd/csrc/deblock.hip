@@ -388,8 +388,8 @@ int vvhip_deblock( vvhip_ctx* ctx, const vvhip_deblock_plane* planes, int n_plan
         o.qp[0] = q.qp[0]; o.qp[1] = q.qp[1]; o.qp[2] = q.qp[2]; o.bs = q.bs & 0x3f; o.len = q.side_max_filt_length; o.flags = q.flags; o.pad[0] = o.pad[1] = 0;
       }
   }
-  vvhip_ctx::SaoSlot& S = ctx->saoSlot[2];
-  const int rc = saoUpload( ctx, S, dev.data(), dev.size() * sizeof( DbkRec ) );
+  HostList& S = ctx->list[LIST_DEBLOCK];
+  const int rc = listUpload( ctx, S, ListBlob( dev.data(), dev.size() * sizeof( DbkRec ) ) );
   if( rc != VVHIP_OK ) return rc;
   A.mapW = mapW; A.unitRow0 = unitRow0; A.ctusX = ctusX; A.ctuRow0 = ctu_row0; A.ctu = ctu_size; A.bitDepth = bit_depth; A.nPlanes = n_planes;
   const dim3 grid( ctusX * n_rows, n_planes );
@@ -408,7 +408,7 @@ int vvhip_deblock( vvhip_ctx* ctx, const vvhip_deblock_plane* planes, int n_plan
     hipLaunchKernelGGL( dbkKernel<false>, grid, dim3( DBK_THREADS ), lds, ctx->stream, A );
     VVHIP_LAUNCH_CHECK( ctx );
   }
-  return saoMark( ctx, S );
+  return listLaunched( ctx, S );
 }
 
 } // extern "C"

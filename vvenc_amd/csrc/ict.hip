@@ -170,14 +170,15 @@ ictInvKernel( const IctDev* __restrict__ items, const IctUnit* __restrict__ unit
 // samples of alignment of an offset / a pointer, capped at 8 (16 bytes)
 inline int ictAlignOf( uint64_t v ) { return v == 0 ? 8 : ( int ) std::min<uint64_t>( 8, v & ( ~v + 1 ) ); }
 
-struct IctKeyed { uint32_t cls; int32_t pos; int idx; };
+struct IctHead { size_t offItems, offUnits; int units; };      // the head of a schedule's blob: where the sorted items and the wave units lie, the number of units
+
+inline HostList& ictSlot( vvhip_ctx* ctx, int dir ) { return ctx->list[dir ? LIST_ICT_INV : LIST_ICT_FWD]; }
 
 // validates the list, derives the schedule and uploads it; on success the slot's key names the list it belongs to
 int ictBuildSchedule( vvhip_ctx* ctx, const char* entry, int dir, const vvhip_ict_item* items_host, int n, int ptrAlign, std::vector<unsigned char>& key )
 {
-  vvhip_ctx::IctSched& S = ctx->ictSched[dir];
   std::vector<IctDev> dev( n );
-  std::vector<IctKeyed> order( n );
+  std::vector<ListKeyed> order( n );
   for( int i = 0; i < n; i++ )
   {
     const vvhip_ict_item& it = items_host[i];
@@ -199,7 +200,7 @@ int ictBuildSchedule( vvhip_ctx* ctx, const char* entry, int dir, const vvhip_ic
     order[i].pos = it.cb_off;
     order[i].idx = i;
   }
-  std::sort( order.begin(), order.end(), []( const IctKeyed& a, const IctKeyed& b ) { return a.cls != b.cls ? a.cls < b.cls : a.pos != b.pos ? a.pos < b.pos : a.idx < b.idx; } );
+  std::sort( order.begin(), order.end() );
 
   std::vector<IctDev> sorted( n );
   std::vector<IctUnit> units;
@@ -221,55 +222,23 @@ int ictBuildSchedule( vvhip_ctx* ctx, const char* entry, int dir, const vvhip_ic
   IctUnit none; memset( &none, 0, sizeof( none ) );
   while( units.size() & 3 ) units.push_back( none );      // four waves per workgroup
 
-  // ---- device copy of the schedule: grow-only; the host copy stays alive as the source of the asynchronous upload
-  const size_t bItems = ( sorted.size() * sizeof( IctDev ) + 255 ) & ~( size_t ) 255, bAll = bItems + units.size() * sizeof( IctUnit );
-  if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipEventSynchronize( S.event ) );      // the last launch that reads the old schedule, whatever stream it went to
-  S.key.clear();
-  if( bAll > S.bytes )
-  {
-    if( S.d_sched ) ( void ) hipFree( S.d_sched );
-    S.d_sched = nullptr; S.bytes = 0;
-    const size_t want = bAll + bAll / 4;
-    VVHIP_CHECK_HIP( ctx, hipMalloc( &S.d_sched, want ) );
-    S.bytes = want;
-  }
-  S.blob.assign( bAll, 0 );
-  memcpy( S.blob.data(), sorted.data(), sorted.size() * sizeof( IctDev ) );
-  memcpy( S.blob.data() + bItems, units.data(), units.size() * sizeof( IctUnit ) );
-  VVHIP_CHECK_HIP( ctx, hipMemcpyAsync( S.d_sched, S.blob.data(), S.blob.size(), hipMemcpyHostToDevice, ctx->stream ) );
-  S.stream = ctx->stream;
-  S.offUnits = bItems; S.units = ( int ) units.size();
-  S.key.swap( key );
-  return VVHIP_OK;
+  IctHead H;
+  ListBlob blob( &H, sizeof( H ) );
+  H.offItems = blob.add( sorted.data(), sorted.size() * sizeof( IctDev ) );
+  H.offUnits = blob.add( units.data(), units.size() * sizeof( IctUnit ) );
+  H.units = ( int ) units.size();
+  return listUpload( ctx, ictSlot( ctx, dir ), blob, &key );
 }
 
 // the list's key: the direction's pointer alignment + the items; -> the schedule is current and ordered in front of the launch on the context's stream
 int ictSchedule( vvhip_ctx* ctx, const char* entry, int dir, const vvhip_ict_item* items_host, int n, int ptrAlign )
 {
-  vvhip_ctx::IctSched& S = ctx->ictSched[dir];
   std::vector<unsigned char> key( 1 + ( size_t ) n * sizeof( vvhip_ict_item ) );
   key[0] = ( unsigned char ) ptrAlign;
   memcpy( key.data() + 1, items_host, ( size_t ) n * sizeof( vvhip_ict_item ) );
-  if( key != S.key ) return ictBuildSchedule( ctx, entry, dir, items_host, n, ptrAlign, key );
-  if( S.stream != ctx->stream )      // same schedule, other stream: order it behind the upload
-  {
-    if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipStreamWaitEvent( ctx->stream, S.event, 0 ) );
-    S.stream = ctx->stream;
-  }
-  return VVHIP_OK;
-}
-
-int ictLaunched( vvhip_ctx* ctx, vvhip_ctx::IctSched& S )
-{
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if( hipStreamIsCapturing( ctx->stream, &cap ) != hipSuccess ) cap = hipStreamCaptureStatusNone;
-  if( cap == hipStreamCaptureStatusNone )      // (a launch recorded into a graph runs later: the graph's owner keeps the list unchanged while the graph is in use)
-  {
-    if( !S.event ) VVHIP_CHECK_HIP( ctx, hipEventCreateWithFlags( &S.event, hipEventDisableTiming ) );
-    VVHIP_CHECK_HIP( ctx, hipEventRecord( S.event, ctx->stream ) );
-    S.eventRecorded = true;
-  }
-  return VVHIP_OK;
+  bool current = false;
+  const int rc = listCurrent( ctx, ictSlot( ctx, dir ), key, &current );
+  return rc || current ? rc : ictBuildSchedule( ctx, entry, dir, items_host, n, ptrAlign, key );
 }
 
 inline int ictPtrAlign( std::initializer_list<const void*> ptrs )
@@ -295,12 +264,13 @@ int vvhip_ict_fwd_batch( vvhip_ctx* ctx, const int16_t* d_resi, const vvhip_ict_
       if( items_host[i].mode != 0 ) return vvhip_fail( ctx, VVHIP_E_ARG, "%s: item %d has ICT mode %d and there is no buffer for the joint blocks", entry, i, items_host[i].mode );
   const int rc = ictSchedule( ctx, entry, 0, items_host, n, ictPtrAlign( { d_resi, d_joint } ) );
   if( rc ) return rc;
-  vvhip_ctx::IctSched& S = ctx->ictSched[0];
-  const char* base = static_cast<const char*>( S.d_sched );
-  hipLaunchKernelGGL( ictFwdKernel, dim3( ( unsigned ) ( S.units / 4 ) ), dim3( 256 ), 0, ctx->stream, reinterpret_cast<const IctDev*>( base ),
-                      reinterpret_cast<const IctUnit*>( base + S.offUnits ), d_resi, d_joint, d_dist );
+  HostList& S = ictSlot( ctx, 0 );
+  const IctHead& H = listHead<IctHead>( S );
+  const char* base = static_cast<const char*>( S.d );
+  hipLaunchKernelGGL( ictFwdKernel, dim3( ( unsigned ) ( H.units / 4 ) ), dim3( 256 ), 0, ctx->stream, reinterpret_cast<const IctDev*>( base + H.offItems ),
+                      reinterpret_cast<const IctUnit*>( base + H.offUnits ), d_resi, d_joint, d_dist );
   VVHIP_LAUNCH_CHECK( ctx );
-  return ictLaunched( ctx, S );
+  return listLaunched( ctx, S );
 }
 
 int vvhip_ict_inv_batch( vvhip_ctx* ctx, const int16_t* d_joint_rec, const vvhip_ict_item* items_host, int n, const vvhip_tu_stats* d_stats, int16_t* d_rec,
@@ -318,12 +288,13 @@ int vvhip_ict_inv_batch( vvhip_ctx* ctx, const int16_t* d_joint_rec, const vvhip
       if( items_host[i].stats_idx >= 0 ) return vvhip_fail( ctx, VVHIP_E_ARG, "%s: item %d names statistics entry %d and there are no statistics", entry, i, items_host[i].stats_idx );
   const int rc = ictSchedule( ctx, entry, 1, items_host, n, ictPtrAlign( { d_joint_rec, d_rec, d_sse ? d_org_resi : nullptr } ) );
   if( rc ) return rc;
-  vvhip_ctx::IctSched& S = ctx->ictSched[1];
-  const char* base = static_cast<const char*>( S.d_sched );
-  hipLaunchKernelGGL( ictInvKernel, dim3( ( unsigned ) ( S.units / 4 ) ), dim3( 256 ), 0, ctx->stream, reinterpret_cast<const IctDev*>( base ),
-                      reinterpret_cast<const IctUnit*>( base + S.offUnits ), d_joint_rec, d_stats, d_rec, d_sse ? d_org_resi : nullptr, d_sse );
+  HostList& S = ictSlot( ctx, 1 );
+  const IctHead& H = listHead<IctHead>( S );
+  const char* base = static_cast<const char*>( S.d );
+  hipLaunchKernelGGL( ictInvKernel, dim3( ( unsigned ) ( H.units / 4 ) ), dim3( 256 ), 0, ctx->stream, reinterpret_cast<const IctDev*>( base + H.offItems ),
+                      reinterpret_cast<const IctUnit*>( base + H.offUnits ), d_joint_rec, d_stats, d_rec, d_sse ? d_org_resi : nullptr, d_sse );
   VVHIP_LAUNCH_CHECK( ctx );
-  return ictLaunched( ctx, S );
+  return listLaunched( ctx, S );
 }
 
 } // extern "C"

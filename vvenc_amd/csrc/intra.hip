@@ -298,12 +298,12 @@ int vvhip_intra_luma_modes_batch( vvhip_ctx* ctx, const vvhip_intra_item* items_
     if( !d_pred && ( q.pred_mask[0] | q.pred_mask[1] | q.pred_mask[2] ) ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_intra_luma_modes_batch: item %d asks for predictions, d_pred is missing", i );
   }
   if( n == 0 ) return VVHIP_OK;
-  vvhip_ctx::SaoSlot& S = ctx->saoSlot[5];
-  const int rc = saoUpload( ctx, S, items_host, ( size_t ) n * sizeof( vvhip_intra_item ) );
+  HostList& S = ctx->list[LIST_INTRA];
+  const int rc = listUpload( ctx, S, ListBlob( items_host, ( size_t ) n * sizeof( vvhip_intra_item ) ) );
   if( rc != VVHIP_OK ) return rc;
   hipLaunchKernelGGL( intraModesKernel, dim3( ( unsigned ) n ), dim3( IN_THREADS ), 0, ctx->stream, ( const vvhip_intra_item* ) S.d, d_ref, d_org, d_pred, d_cost );
   VVHIP_LAUNCH_CHECK( ctx );
-  return saoMark( ctx, S );
+  return listLaunched( ctx, S );
 }
 
 } // extern "C"

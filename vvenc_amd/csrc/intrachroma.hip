@@ -362,12 +362,12 @@ int vvhip_intra_chroma_modes_batch( vvhip_ctx* ctx, const vvhip_intra_chroma_ite
     if( q.pred_mask && !d_pred ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_intra_chroma_modes_batch: item %d asks for predictions, d_pred is missing", i );
   }
   if( n == 0 ) return VVHIP_OK;
-  vvhip_ctx::SaoSlot& S = ctx->saoSlot[6];
-  const int rc = saoUpload( ctx, S, items_host, ( size_t ) n * sizeof( vvhip_intra_chroma_item ) );
+  HostList& S = ctx->list[LIST_INTRA_CHROMA];
+  const int rc = listUpload( ctx, S, ListBlob( items_host, ( size_t ) n * sizeof( vvhip_intra_chroma_item ) ) );
   if( rc != VVHIP_OK ) return rc;
   hipLaunchKernelGGL( intraChromaModesKernel, dim3( ( unsigned ) n ), dim3( IC_THREADS ), 0, ctx->stream, ( const vvhip_intra_chroma_item* ) S.d, d_luma, d_ref, d_org, d_pred, d_cost );
   VVHIP_LAUNCH_CHECK( ctx );
-  return saoMark( ctx, S );
+  return listLaunched( ctx, S );
 }
 
 } // extern "C"

@@ -705,7 +705,13 @@ std::vector<int> predBandOrder( int nGroups, int base )      // (shared with pre
 }
 namespace {
 
-struct Keyed { uint32_t cls; int64_t pos; int idx; };
+// the head of the schedule's blob: where its sections lie and what the launches need to know of them.  One unit table: the plain units, then the units of items with an
+// extension (BDOF, DMVR's padded reference), of BCW / GEO items, of CIIP items — a kernel of its own each, with its own LDS per wave
+struct PredHead
+{
+  size_t offItems, offSubs, offUnits, offBlend, offCiip;
+  int    units, ldsPerWave, unitsEx, ldsPerWaveEx, unitsBlend, ldsPerWaveBlend, unitsCiip, ldsPerWaveCiip;
+};
 
 // ---- GEO: split direction + CU size -> the weight line of one component block (host) ----
 // The reference reads g_globalGeoWeights[mask][my * 112 + mx] with mx = offX + X ( 111 - offX - X under mirror 1 ), my = offY + Y ( 111 - offY - Y under mirror 2 ),
@@ -740,12 +746,12 @@ void geoLine( int splitDir, int log2CuW, int log2CuH, int chroma, PredBlendDev& 
 const int8_t kBcwW1[5] = { -2, 3, 4, 5, 10 };      // g_BcwWeights (Rom.cpp:1152)
 
 // validates the list, derives the schedule and uploads it; on success the context's key names the list (items + plane table) the device copy belongs to
-int predBuildSchedule( vvhip_ctx* ctx, vvhip_ctx::PredSched& S, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host,
+int predBuildSchedule( vvhip_ctx* ctx, HostList& S, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host,
                        const vvhip_pred_blend* blend_host, const vvhip_pred_ciip* ciip_host, const int16_t* d_intra_ref, int n, std::vector<unsigned char>& key )
 {
   // ---- validation + plane table resolved; nothing is launched when any item is unsupported
   std::vector<PredDev> dev( n );
-  std::vector<Keyed> order( n );
+  std::vector<ListKeyed> order( n );
   std::vector<PredBlendDev> blendDev( blend_host ? n : 0 );
   std::vector<PredCiipDev> ciipDev( ciip_host ? n : 0 );
   for( int i = 0; i < n; i++ )
@@ -858,7 +864,7 @@ int predBuildSchedule( vvhip_ctx* ctx, vvhip_ctx::PredSched& S, const vvhip_me_p
     order[i].pos = ( ( int64_t ) it.ref_off[l0] << 5 ) | ( uint32_t ) ( it.ref_plane[l0] & 31 );
     order[i].idx = i;
   }
-  std::sort( order.begin(), order.end(), []( const Keyed& a, const Keyed& b ) { return a.cls != b.cls ? a.cls < b.cls : a.pos != b.pos ? a.pos < b.pos : a.idx < b.idx; } );
+  std::sort( order.begin(), order.end() );
 
   // ---- schedule: per class the tiles in picture order, 64 lanes' worth per wave, four waves per workgroup, workgroups dealt to the XCDs in bands
   //      classes with an extension flag go to a list of their own, which predListExKernel runs; a BDOF block is cut into its 16x16 / 16x8 / 8x16 units (xSubPuBDOF :326-357)
@@ -899,38 +905,21 @@ int predBuildSchedule( vvhip_ctx* ctx, vvhip_ctx::PredSched& S, const vvhip_me_p
     c0 = c1;
   }
 
-  // ---- device copy of the schedule: grow-only; the host copy stays alive as the source of the asynchronous upload
-  std::vector<PredUnit> units( unitsPlain );      // one table: the plain units, then the units of the extension kernel, then those of the blend kernel, then those of the CIIP kernel
+  // ---- the blob: head, items, tiles, units, blend records, CIIP records right behind those
+  std::vector<PredUnit> units( unitsPlain );
   units.insert( units.end(), unitsEx.begin(), unitsEx.end() );
   units.insert( units.end(), unitsBlend.begin(), unitsBlend.end() );
   units.insert( units.end(), unitsCiip.begin(), unitsCiip.end() );
-  const size_t bItems = ( dev.size() * sizeof( PredDev ) + 255 ) & ~( size_t ) 255, bSubs = ( subs.size() * sizeof( PredSub ) + 255 ) & ~( size_t ) 255;
-  const size_t bUnits = ( units.size() * sizeof( PredUnit ) + 255 ) & ~( size_t ) 255, bBlend = blendDev.size() * sizeof( PredBlendDev ), bCiip = ciipDev.size() * sizeof( PredCiipDev );
-  const size_t bAll = bItems + bSubs + bUnits + bBlend + bCiip;
-  if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipEventSynchronize( S.event ) );      // the last launch that reads the old schedule, whatever stream it went to
-  S.key.clear();
-  if( bAll > S.bytes )
-  {
-    if( S.d_sched ) ( void ) hipFree( S.d_sched );
-    S.d_sched = nullptr; S.bytes = 0;
-    const size_t want = bAll + bAll / 4;
-    VVHIP_CHECK_HIP( ctx, hipMalloc( &S.d_sched, want ) );
-    S.bytes = want;
-  }
-  S.blob.assign( bAll, 0 );
-  memcpy( S.blob.data(), dev.data(), dev.size() * sizeof( PredDev ) );
-  memcpy( S.blob.data() + bItems, subs.data(), subs.size() * sizeof( PredSub ) );
-  memcpy( S.blob.data() + bItems + bSubs, units.data(), units.size() * sizeof( PredUnit ) );
-  if( bBlend ) memcpy( S.blob.data() + bItems + bSubs + bUnits, blendDev.data(), bBlend );
-  if( bCiip ) memcpy( S.blob.data() + bItems + bSubs + bUnits + bBlend, ciipDev.data(), bCiip );
-  VVHIP_CHECK_HIP( ctx, hipMemcpyAsync( S.d_sched, S.blob.data(), S.blob.size(), hipMemcpyHostToDevice, ctx->stream ) );
-  S.stream = ctx->stream;
-  S.offSubs = bItems; S.offUnits = bItems + bSubs; S.offBlend = bItems + bSubs + bUnits; S.units = ( int ) unitsPlain.size(); S.ldsPerWave = ldsPerWave;
-  S.unitsEx = ( int ) unitsEx.size(); S.ldsPerWaveEx = ldsPerWaveEx;
-  S.unitsBlend = ( int ) unitsBlend.size(); S.ldsPerWaveBlend = ldsPerWaveBlend;
-  S.offCiip = S.offBlend + bBlend; S.unitsCiip = ( int ) unitsCiip.size(); S.ldsPerWaveCiip = ldsPerWaveCiip;
-  S.key.swap( key );
-  return VVHIP_OK;
+  PredHead H;
+  ListBlob blob( &H, sizeof( H ) );
+  H.offItems = blob.add( dev.data(), dev.size() * sizeof( PredDev ) );
+  H.offSubs = blob.add( subs.data(), subs.size() * sizeof( PredSub ) );
+  H.offUnits = blob.add( units.data(), units.size() * sizeof( PredUnit ) );
+  H.offBlend = blob.add( blendDev.data(), blendDev.size() * sizeof( PredBlendDev ) );
+  H.offCiip = blob.add( ciipDev.data(), ciipDev.size() * sizeof( PredCiipDev ), sizeof( PredBlendDev ) );
+  H.units = ( int ) unitsPlain.size(); H.ldsPerWave = ldsPerWave; H.unitsEx = ( int ) unitsEx.size(); H.ldsPerWaveEx = ldsPerWaveEx;
+  H.unitsBlend = ( int ) unitsBlend.size(); H.ldsPerWaveBlend = ldsPerWaveBlend; H.unitsCiip = ( int ) unitsCiip.size(); H.ldsPerWaveCiip = ldsPerWaveCiip;
+  return listUpload( ctx, S, blob, &key );
 }
 
 int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_item* items_host, const vvhip_pred_ext* ext_host,
@@ -950,7 +939,7 @@ int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_pla
   //      (the extensions are part of the list: the same items with other extensions are another schedule)
   //      A list with a blend array keeps a schedule of its own (and its array is part of its key), and so does a list with a CIIP array.  The intra reference samples are
   //      device data like the planes: their address and contents are not part of the key (the address is a kernel argument of every launch).
-  vvhip_ctx::PredSched& S = ctx->predSched[ciip_host ? 2 : blend_host ? 1 : 0];
+  HostList& S = ctx->list[ciip_host ? LIST_PRED_CIIP : blend_host ? LIST_PRED_BLEND : LIST_PRED];
   const size_t bKeyItems = sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ) + ( size_t ) n * sizeof( vvhip_pred_item ), bKeyExt = ext_host ? ( size_t ) n * sizeof( vvhip_pred_ext ) : 0;
   const size_t bKeyBlend = blend_host ? 1 + ( size_t ) n * sizeof( vvhip_pred_blend ) : 0;
   std::vector<unsigned char> key( bKeyItems + bKeyExt + bKeyBlend + ( ciip_host ? 2 + ( size_t ) n * sizeof( vvhip_pred_ciip ) : 0 ) );
@@ -965,58 +954,44 @@ int predInterBatch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_pla
   memcpy( key.data(), &n_planes, sizeof( int ) );
   memcpy( key.data() + sizeof( int ), planes_host, ( size_t ) n_planes * sizeof( vvhip_me_plane ) );
   memcpy( key.data() + sizeof( int ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ), items_host, ( size_t ) n * sizeof( vvhip_pred_item ) );
-  if( key != S.key )
-  {
-    const int rc = predBuildSchedule( ctx, S, planes_host, n_planes, items_host, ext_host, blend_host, ciip_host, d_intra_ref, n, key );
-    if( rc ) return rc;
-  }
-  else if( S.stream != ctx->stream )      // same schedule, other stream: order it behind the upload
-  {
-    if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipStreamWaitEvent( ctx->stream, S.event, 0 ) );
-    S.stream = ctx->stream;
-  }
-  if( S.unitsCiip && !d_intra_ref ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ciip: the list has CIIP items and there are no intra reference samples" );
-  const size_t bItems = S.offSubs, bSubs = S.offUnits - S.offSubs;
-  const int ldsPerWave = S.ldsPerWave, nUnits = S.units;
+  bool current = false;
+  int rc = listCurrent( ctx, S, key, &current );
+  if( rc == VVHIP_OK && !current ) rc = predBuildSchedule( ctx, S, planes_host, n_planes, items_host, ext_host, blend_host, ciip_host, d_intra_ref, n, key );
+  if( rc ) return rc;
+  const PredHead& H = listHead<PredHead>( S );
+  if( H.unitsCiip && !d_intra_ref ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_pred_inter_batch_ciip: the list has CIIP items and there are no intra reference samples" );
+  const char* base = static_cast<const char*>( S.d );
+  const PredUnit* units = reinterpret_cast<const PredUnit*>( base + H.offUnits );
   PredArgs a;
-  const char* base = static_cast<const char*>( S.d_sched );
-  a.items = reinterpret_cast<const PredDev*>( base ); a.subs = reinterpret_cast<const PredSub*>( base + bItems ); a.units = reinterpret_cast<const PredUnit*>( base + bItems + bSubs );
-  a.nUnits = nUnits; a.bitDepth = bit_depth; a.ldsPerWave = ldsPerWave;
+  a.items = reinterpret_cast<const PredDev*>( base + H.offItems ); a.subs = reinterpret_cast<const PredSub*>( base + H.offSubs ); a.bitDepth = bit_depth;
   a.pred = d_pred; a.predStride = pred_stride; a.org = d_resi ? d_org : nullptr; a.orgStride = org_stride; a.resi = d_resi;
-  if( nUnits )
+  if( H.units )
   {
-    hipLaunchKernelGGL( predListKernel, dim3( ( unsigned ) ( nUnits / 4 ) ), dim3( 256 ), ( size_t ) ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a );
+    a.units = units; a.nUnits = H.units; a.ldsPerWave = H.ldsPerWave;
+    hipLaunchKernelGGL( predListKernel, dim3( ( unsigned ) ( a.nUnits / 4 ) ), dim3( 256 ), ( size_t ) a.ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a );
     VVHIP_LAUNCH_CHECK( ctx );
   }
-  if( S.unitsEx )
+  if( H.unitsEx )
   {
-    a.units += nUnits; a.nUnits = S.unitsEx; a.ldsPerWave = S.ldsPerWaveEx;
+    a.units = units + H.units; a.nUnits = H.unitsEx; a.ldsPerWave = H.ldsPerWaveEx;
     hipLaunchKernelGGL( predListExKernel, dim3( ( unsigned ) ( a.nUnits / 4 ) ), dim3( 256 ), ( size_t ) a.ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a );
     VVHIP_LAUNCH_CHECK( ctx );
   }
-  if( S.unitsBlend )
+  if( H.unitsBlend )
   {
-    a.units = reinterpret_cast<const PredUnit*>( base + bItems + bSubs ) + nUnits + S.unitsEx; a.nUnits = S.unitsBlend; a.ldsPerWave = S.ldsPerWaveBlend;
+    a.units = units + H.units + H.unitsEx; a.nUnits = H.unitsBlend; a.ldsPerWave = H.ldsPerWaveBlend;
     hipLaunchKernelGGL( predListBlendKernel, dim3( ( unsigned ) ( a.nUnits / 4 ) ), dim3( 256 ), ( size_t ) a.ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a,
-                        reinterpret_cast<const PredBlendDev*>( base + S.offBlend ) );
+                        reinterpret_cast<const PredBlendDev*>( base + H.offBlend ) );
     VVHIP_LAUNCH_CHECK( ctx );
   }
-  if( S.unitsCiip )
+  if( H.unitsCiip )
   {
-    a.units = reinterpret_cast<const PredUnit*>( base + bItems + bSubs ) + nUnits + S.unitsEx + S.unitsBlend; a.nUnits = S.unitsCiip; a.ldsPerWave = S.ldsPerWaveCiip;
+    a.units = units + H.units + H.unitsEx + H.unitsBlend; a.nUnits = H.unitsCiip; a.ldsPerWave = H.ldsPerWaveCiip;
     hipLaunchKernelGGL( predListCiipKernel, dim3( ( unsigned ) ( a.nUnits / 4 ) ), dim3( 256 ), ( size_t ) a.ldsPerWave * 4 * sizeof( int16_t ), ctx->stream, a,
-                        reinterpret_cast<const PredCiipDev*>( base + S.offCiip ), d_intra_ref );
+                        reinterpret_cast<const PredCiipDev*>( base + H.offCiip ), d_intra_ref );
     VVHIP_LAUNCH_CHECK( ctx );
   }
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if( hipStreamIsCapturing( ctx->stream, &cap ) != hipSuccess ) cap = hipStreamCaptureStatusNone;
-  if( cap == hipStreamCaptureStatusNone )      // (a launch recorded into a graph runs later: the graph's owner keeps the list unchanged while the graph is in use)
-  {
-    if( !S.event ) VVHIP_CHECK_HIP( ctx, hipEventCreateWithFlags( &S.event, hipEventDisableTiming ) );
-    VVHIP_CHECK_HIP( ctx, hipEventRecord( S.event, ctx->stream ) );
-    S.eventRecorded = true;
-  }
-  return VVHIP_OK;
+  return listLaunched( ctx, S );
 }
 
 } // namespace

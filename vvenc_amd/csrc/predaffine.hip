@@ -387,14 +387,14 @@ predAffineKernel( AffArgs a )
   else           affBody<6>( L, a );
 }
 
-struct AffKeyed { uint32_t cls; int64_t pos; int idx; };
+struct AffHead { size_t offItems, offSubs, offUnits; int units; };      // the head of the schedule's blob: where its sections lie, the number of wave units
 
 // validates the list, derives the schedule and uploads it; on success the context's key names the list the device copy belongs to
 int affBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_pred_affine_item* items_host, int n, int pic_width, int pic_height,
                       std::vector<unsigned char>& key )
 {
   std::vector<AffDev> dev( n );
-  std::vector<AffKeyed> order( n );
+  std::vector<ListKeyed> order( n );
   for( int i = 0; i < n; i++ )
   {
     const vvhip_pred_affine_item& it = items_host[i];
@@ -430,7 +430,7 @@ int affBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_p
     order[i].pos = ( ( int64_t ) it.cu_y << 20 ) | ( uint32_t ) it.cu_x;
     order[i].idx = i;
   }
-  std::sort( order.begin(), order.end(), []( const AffKeyed& a, const AffKeyed& b ) { return a.cls != b.cls ? a.cls < b.cls : a.pos != b.pos ? a.pos < b.pos : a.idx < b.idx; } );
+  std::sort( order.begin(), order.end() );
 
   // ---- schedule: per class the tiles in picture order, sixteen sub-blocks per wave, four waves per workgroup, workgroups dealt to the XCDs in bands
   std::vector<AffSub> subs;
@@ -460,28 +460,14 @@ int affBuildSchedule( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_p
     c0 = c1;
   }
 
-  // ---- device copy of the schedule: grow-only; the host copy stays alive as the source of the asynchronous upload.  Its own buffer, key and event: the schedule of
-  //      vvhip_pred_inter_batch on the same context is not touched
-  const size_t bItems = ( dev.size() * sizeof( AffDev ) + 255 ) & ~( size_t ) 255, bSubs = ( subs.size() * sizeof( AffSub ) + 255 ) & ~( size_t ) 255, bUnits = units.size() * sizeof( AffUnit );
-  if( ctx->affEventRecorded ) VVHIP_CHECK_HIP( ctx, hipEventSynchronize( ctx->affEvent ) );      // the last launch that reads the old schedule, whatever stream it went to
-  ctx->affKey.clear();
-  if( bItems + bSubs + bUnits > ctx->affBytes )
-  {
-    if( ctx->d_affSched ) ( void ) hipFree( ctx->d_affSched );
-    ctx->d_affSched = nullptr; ctx->affBytes = 0;
-    const size_t want = ( bItems + bSubs + bUnits ) + ( bItems + bSubs + bUnits ) / 4;
-    VVHIP_CHECK_HIP( ctx, hipMalloc( &ctx->d_affSched, want ) );
-    ctx->affBytes = want;
-  }
-  ctx->affBlob.assign( bItems + bSubs + bUnits, 0 );
-  memcpy( ctx->affBlob.data(), dev.data(), dev.size() * sizeof( AffDev ) );
-  memcpy( ctx->affBlob.data() + bItems, subs.data(), subs.size() * sizeof( AffSub ) );
-  memcpy( ctx->affBlob.data() + bItems + bSubs, units.data(), bUnits );
-  VVHIP_CHECK_HIP( ctx, hipMemcpyAsync( ctx->d_affSched, ctx->affBlob.data(), ctx->affBlob.size(), hipMemcpyHostToDevice, ctx->stream ) );
-  ctx->affStream = ctx->stream;
-  ctx->affOffSubs = bItems; ctx->affOffUnits = bItems + bSubs; ctx->affUnits = ( int ) units.size();
-  ctx->affKey.swap( key );
-  return VVHIP_OK;
+  // ---- the blob: head, items, tiles, units.  A slot of its own: the schedules of vvhip_pred_inter_batch on the same context are not touched
+  AffHead H;
+  ListBlob blob( &H, sizeof( H ) );
+  H.offItems = blob.add( dev.data(), dev.size() * sizeof( AffDev ) );
+  H.offSubs = blob.add( subs.data(), subs.size() * sizeof( AffSub ) );
+  H.offUnits = blob.add( units.data(), units.size() * sizeof( AffUnit ) );
+  H.units = ( int ) units.size();
+  return listUpload( ctx, ctx->list[LIST_AFFINE], blob, &key );
 }
 
 } // namespace
@@ -509,32 +495,20 @@ int vvhip_pred_affine_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, 
   memcpy( key.data(), head, sizeof( head ) );
   memcpy( key.data() + sizeof( head ), planes_host, ( size_t ) n_planes * sizeof( vvhip_me_plane ) );
   memcpy( key.data() + sizeof( head ) + ( size_t ) n_planes * sizeof( vvhip_me_plane ), items_host, ( size_t ) n * sizeof( vvhip_pred_affine_item ) );
-  if( key != ctx->affKey )
-  {
-    const int rc = affBuildSchedule( ctx, planes_host, n_planes, items_host, n, pic_width, pic_height, key );
-    if( rc ) return rc;
-  }
-  else if( ctx->affStream != ctx->stream )      // same schedule, other stream: order it behind the upload
-  {
-    if( ctx->affEventRecorded ) VVHIP_CHECK_HIP( ctx, hipStreamWaitEvent( ctx->stream, ctx->affEvent, 0 ) );
-    ctx->affStream = ctx->stream;
-  }
+  HostList& S = ctx->list[LIST_AFFINE];
+  bool current = false;
+  int rc = listCurrent( ctx, S, key, &current );
+  if( rc == VVHIP_OK && !current ) rc = affBuildSchedule( ctx, planes_host, n_planes, items_host, n, pic_width, pic_height, key );
+  if( rc ) return rc;
+  const AffHead& H = listHead<AffHead>( S );
+  const char* base = static_cast<const char*>( S.d );
   AffArgs a;
-  const char* base = static_cast<const char*>( ctx->d_affSched );
-  a.items = reinterpret_cast<const AffDev*>( base ); a.subs = reinterpret_cast<const AffSub*>( base + ctx->affOffSubs ); a.units = reinterpret_cast<const AffUnit*>( base + ctx->affOffUnits );
-  a.nUnits = ctx->affUnits; a.bitDepth = bit_depth; a.picW = pic_width; a.picH = pic_height; a.ctu = ctu_size;
+  a.items = reinterpret_cast<const AffDev*>( base + H.offItems ); a.subs = reinterpret_cast<const AffSub*>( base + H.offSubs ); a.units = reinterpret_cast<const AffUnit*>( base + H.offUnits );
+  a.nUnits = H.units; a.bitDepth = bit_depth; a.picW = pic_width; a.picH = pic_height; a.ctu = ctu_size;
   a.pred = d_pred; a.predStride = pred_stride; a.org = d_resi ? d_org : nullptr; a.orgStride = org_stride; a.resi = d_resi;
   hipLaunchKernelGGL( predAffineKernel, dim3( ( unsigned ) ( a.nUnits / 4 ) ), dim3( 256 ), 0, ctx->stream, a );
   VVHIP_LAUNCH_CHECK( ctx );
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if( hipStreamIsCapturing( ctx->stream, &cap ) != hipSuccess ) cap = hipStreamCaptureStatusNone;
-  if( cap == hipStreamCaptureStatusNone )      // (a launch recorded into a graph runs later: the graph's owner keeps the list unchanged while the graph is in use)
-  {
-    if( !ctx->affEvent ) VVHIP_CHECK_HIP( ctx, hipEventCreateWithFlags( &ctx->affEvent, hipEventDisableTiming ) );
-    VVHIP_CHECK_HIP( ctx, hipEventRecord( ctx->affEvent, ctx->stream ) );
-    ctx->affEventRecorded = true;
-  }
-  return VVHIP_OK;
+  return listLaunched( ctx, S );
 }
 
 } // extern "C"

@@ -261,40 +261,6 @@ saoOffsetKernel( const SaoOffsetArgs a )
     }
 }
 
-} // namespace
-
-// (shared with deblock.hip: declared in common.h)
-// the per-call host array of an entry -> the context's device slot: grow-only, the host copy stays alive as the source of the asynchronous upload, and the event of the
-// last launch that read the slot is waited for before either is rewritten
-int saoUpload( vvhip_ctx* ctx, vvhip_ctx::SaoSlot& S, const void* data, size_t bytes )
-{
-  if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipEventSynchronize( S.event ) );
-  if( bytes > S.bytes )
-  {
-    if( S.d ) ( void ) hipFree( S.d );
-    S.d = nullptr; S.bytes = 0;
-    const size_t want = bytes + bytes / 4 + 256;
-    VVHIP_CHECK_HIP( ctx, hipMalloc( &S.d, want ) );
-    S.bytes = want;
-  }
-  S.blob.assign( ( const unsigned char* ) data, ( const unsigned char* ) data + bytes );
-  VVHIP_CHECK_HIP( ctx, hipMemcpyAsync( S.d, S.blob.data(), bytes, hipMemcpyHostToDevice, ctx->stream ) );
-  return VVHIP_OK;
-}
-
-int saoMark( vvhip_ctx* ctx, vvhip_ctx::SaoSlot& S )
-{
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if( hipStreamIsCapturing( ctx->stream, &cap ) != hipSuccess ) cap = hipStreamCaptureStatusNone;
-  if( cap != hipStreamCaptureStatusNone ) return VVHIP_OK;
-  if( !S.event ) VVHIP_CHECK_HIP( ctx, hipEventCreateWithFlags( &S.event, hipEventDisableTiming ) );
-  VVHIP_CHECK_HIP( ctx, hipEventRecord( S.event, ctx->stream ) );
-  S.eventRecorded = true;
-  return VVHIP_OK;
-}
-
-namespace {
-
 // the geometry rules both entries share; -> the CTU grid
 bool saoGrid( int width, int height, int ctuW, int ctuH, int stride, int* ctusX, int* ctusY )
 {
@@ -344,15 +310,15 @@ int vvhip_sao_stats( vvhip_ctx* ctx, const vvhip_sao_stats_plane* planes, int n_
       const int can = ( L ? F_L : 0 ) | ( T ? F_A : 0 ) | ( L && T ? F_AL : 0 ) | ( R ? F_R : 0 ) | ( B ? F_B : 0 ) | ( T && R ? F_AR : 0 );
       if( f[i] & ~can ) return vvhip_fail( ctx, VVHIP_E_ARG, "vvhip_sao_stats: CTU (%d, %d): flags 0x%02x name a neighbour outside the picture (possible 0x%02x)", cx, cy, f[i], can );
     }
-    const int rc = saoUpload( ctx, ctx->saoSlot[0], f, ( size_t ) nCtus );
+    const int rc = listUpload( ctx, ctx->list[LIST_SAO_FLAGS], ListBlob( f, ( size_t ) nCtus ) );
     if( rc != VVHIP_OK ) return rc;
-    A.flags = ( const uint8_t* ) ctx->saoSlot[0].d;
+    A.flags = ( const uint8_t* ) ctx->list[LIST_SAO_FLAGS].d;
   }
   A.out = ( long long* ) d_out; A.ctuRow0 = ctu_row0; A.nPlanes = n_planes;
   const size_t lds = ( size_t ) ( maxH + 2 ) * ( maxW + 2 * SAO_PAD ) * sizeof( int16_t );
   hipLaunchKernelGGL( saoStatsKernel, dim3( nCtus, n_planes ), dim3( SAO_THREADS ), lds, ctx->stream, A );
   VVHIP_LAUNCH_CHECK( ctx );
-  return flags_host ? saoMark( ctx, ctx->saoSlot[0] ) : VVHIP_OK;
+  return flags_host ? listLaunched( ctx, ctx->list[LIST_SAO_FLAGS] ) : VVHIP_OK;
 }
 
 int vvhip_sao_offset( vvhip_ctx* ctx, const vvhip_sao_offset_plane* planes, int n_planes, const vvhip_sao_param* params_host, int ctu_row0, int n_rows )
@@ -406,14 +372,14 @@ int vvhip_sao_offset( vvhip_ctx* ctx, const vvhip_sao_offset_plane* planes, int 
       for( int k = 0; k < 5; k++ ) o.offs[k] = q.offs[k];
     }
   }
-  const int rc = saoUpload( ctx, ctx->saoSlot[1], dev.data(), dev.size() * sizeof( SaoParamDev ) );
+  const int rc = listUpload( ctx, ctx->list[LIST_SAO_PARAMS], ListBlob( dev.data(), dev.size() * sizeof( SaoParamDev ) ) );
   if( rc != VVHIP_OK ) return rc;
-  A.params = ( const SaoParamDev* ) ctx->saoSlot[1].d;
+  A.params = ( const SaoParamDev* ) ctx->list[LIST_SAO_PARAMS].d;
   A.ctuRow0 = ctu_row0; A.nPlanes = n_planes;
   const size_t lds = ( size_t ) ( maxH + 2 ) * ( maxW + 2 * SAO_PAD ) * sizeof( int16_t );
   hipLaunchKernelGGL( saoOffsetKernel, dim3( nCtus, n_planes ), dim3( SAO_THREADS ), lds, ctx->stream, A );
   VVHIP_LAUNCH_CHECK( ctx );
-  return saoMark( ctx, ctx->saoSlot[1] );
+  return listLaunched( ctx, ctx->list[LIST_SAO_PARAMS] );
 }
 
 } // extern "C"

@@ -297,17 +297,16 @@ int sbtCheckCu( vvhip_ctx* ctx, const char* entry, int i, int width, int height,
   return VVHIP_OK;
 }
 
-struct SbtKeyed { uint32_t cls; int32_t pos; int idx; };
-inline bool sbtKeyedLess( const SbtKeyed& a, const SbtKeyed& b ) { return a.cls != b.cls ? a.cls < b.cls : a.pos != b.pos ? a.pos < b.pos : a.idx < b.idx; }
+struct SbtHead { size_t offItems, offUnits; int units; };      // the head of a schedule's blob: where the sorted items and the wave units lie, the number of units
 // size class: the most samples first (their waves run longest), then shape and the two vector widths — a wave never mixes classes; inside a class in buffer order
 inline uint32_t sbtClass( int log2W, int log2H, int vY, int vC ) { return ( ( uint32_t ) ( 12 - log2W - log2H ) << 12 ) | ( ( uint32_t ) log2W << 8 ) | ( ( uint32_t ) ilog2i( vY ) << 4 ) | ( uint32_t ) ilog2i( vC ); }
 
 // sorts the device items by class, cuts every class into waves and uploads both; on success the slot's key names the list it belongs to
 template<class Dev, class LanesOf>
-int sbtUploadSchedule( vvhip_ctx* ctx, vvhip_ctx::IctSched& S, const std::vector<Dev>& dev, std::vector<SbtKeyed>& order, LanesOf log2LanesOf, std::vector<unsigned char>& key )
+int sbtUploadSchedule( vvhip_ctx* ctx, HostList& S, const std::vector<Dev>& dev, std::vector<ListKeyed>& order, LanesOf log2LanesOf, std::vector<unsigned char>& key )
 {
   const int n = ( int ) dev.size();
-  std::sort( order.begin(), order.end(), sbtKeyedLess );
+  std::sort( order.begin(), order.end() );
   std::vector<Dev> sorted( n );
   std::vector<SbtUnit> units;
   for( int c0 = 0; c0 < n; )
@@ -330,51 +329,12 @@ int sbtUploadSchedule( vvhip_ctx* ctx, vvhip_ctx::IctSched& S, const std::vector
   SbtUnit none; memset( &none, 0, sizeof( none ) );
   while( units.size() & 3 ) units.push_back( none );      // four waves per workgroup
 
-  // ---- device copy of the schedule: grow-only; the host copy stays alive as the source of the asynchronous upload
-  const size_t bItems = ( sorted.size() * sizeof( Dev ) + 255 ) & ~( size_t ) 255, bAll = bItems + units.size() * sizeof( SbtUnit );
-  if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipEventSynchronize( S.event ) );      // the last launch that reads the old schedule, whatever stream it went to
-  S.key.clear();
-  if( bAll > S.bytes )
-  {
-    if( S.d_sched ) ( void ) hipFree( S.d_sched );
-    S.d_sched = nullptr; S.bytes = 0;
-    const size_t want = bAll + bAll / 4;
-    VVHIP_CHECK_HIP( ctx, hipMalloc( &S.d_sched, want ) );
-    S.bytes = want;
-  }
-  S.blob.assign( bAll, 0 );
-  memcpy( S.blob.data(), sorted.data(), sorted.size() * sizeof( Dev ) );
-  memcpy( S.blob.data() + bItems, units.data(), units.size() * sizeof( SbtUnit ) );
-  VVHIP_CHECK_HIP( ctx, hipMemcpyAsync( S.d_sched, S.blob.data(), S.blob.size(), hipMemcpyHostToDevice, ctx->stream ) );
-  S.stream = ctx->stream;
-  S.offUnits = bItems; S.units = ( int ) units.size();
-  S.key.swap( key );
-  return VVHIP_OK;
-}
-
-// -> true: the slot already holds this list's schedule, ordered in front of the next launch on the context's stream
-int sbtScheduleCurrent( vvhip_ctx* ctx, vvhip_ctx::IctSched& S, const std::vector<unsigned char>& key, bool* current )
-{
-  *current = key == S.key;
-  if( *current && S.stream != ctx->stream )      // same schedule, other stream: order it behind the upload
-  {
-    if( S.eventRecorded ) VVHIP_CHECK_HIP( ctx, hipStreamWaitEvent( ctx->stream, S.event, 0 ) );
-    S.stream = ctx->stream;
-  }
-  return VVHIP_OK;
-}
-
-int sbtLaunched( vvhip_ctx* ctx, vvhip_ctx::IctSched& S )
-{
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if( hipStreamIsCapturing( ctx->stream, &cap ) != hipSuccess ) cap = hipStreamCaptureStatusNone;
-  if( cap == hipStreamCaptureStatusNone )      // (a launch recorded into a graph runs later: the graph's owner keeps the list unchanged while the graph is in use)
-  {
-    if( !S.event ) VVHIP_CHECK_HIP( ctx, hipEventCreateWithFlags( &S.event, hipEventDisableTiming ) );
-    VVHIP_CHECK_HIP( ctx, hipEventRecord( S.event, ctx->stream ) );
-    S.eventRecorded = true;
-  }
-  return VVHIP_OK;
+  SbtHead H;
+  ListBlob blob( &H, sizeof( H ) );
+  H.offItems = blob.add( sorted.data(), sorted.size() * sizeof( Dev ) );
+  H.offUnits = blob.add( units.data(), units.size() * sizeof( SbtUnit ) );
+  H.units = ( int ) units.size();
+  return listUpload( ctx, S, blob, &key );
 }
 
 template<class Item>
@@ -425,16 +385,16 @@ int vvhip_sbt_parts_batch( vvhip_ctx* ctx, const int16_t* d_resi, const vvhip_sb
                        ( const void* ) d_resi, ( void* ) d_parts, ( void* ) d_est );
   if( !( chroma_weight >= 0.0 ) || chroma_weight > 65536.0 ) return vvhip_fail( ctx, VVHIP_E_ARG, "%s: chroma weight %g (0..65536)", entry, chroma_weight );
   if( n == 0 ) return VVHIP_OK;
-  vvhip_ctx::IctSched& S = ctx->sbtSched[0];
+  HostList& S = ctx->list[LIST_SBT_PARTS];
   const int ptrAlign = sbtPtrAlign( { d_resi } );
   std::vector<unsigned char> key = sbtKey( ptrAlign, items_host, n );
   bool current = false;
-  int rc = sbtScheduleCurrent( ctx, S, key, &current );
+  int rc = listCurrent( ctx, S, key, &current );
   if( rc ) return rc;
   if( !current )
   {
     std::vector<SbtPartsDev> dev( n );
-    std::vector<SbtKeyed> order( n );
+    std::vector<ListKeyed> order( n );
     for( int i = 0; i < n; i++ )
     {
       const vvhip_sbt_item& it = items_host[i];
@@ -452,12 +412,13 @@ int vvhip_sbt_parts_batch( vvhip_ctx* ctx, const int16_t* d_resi, const vvhip_sb
     rc = sbtUploadSchedule( ctx, S, dev, order, []( int log2W, int log2H, int, int* log2Lanes ) { *log2Lanes = log2W + log2H <= 8 ? 0 : log2W + log2H <= 10 ? 1 : 2; return 4 >> *log2Lanes; }, key );
     if( rc ) return rc;
   }
-  const char* base = static_cast<const char*>( S.d_sched );
-  hipLaunchKernelGGL( sbtPartsKernel, dim3( ( unsigned ) ( S.units / 4 ) ), dim3( 256 ), 0, ctx->stream, reinterpret_cast<const SbtPartsDev*>( base ),
-                      reinterpret_cast<const SbtUnit*>( base + S.offUnits ), d_resi, chroma_weight, reinterpret_cast<unsigned long long*>( d_parts ),
+  const SbtHead& H = listHead<SbtHead>( S );
+  const char* base = static_cast<const char*>( S.d );
+  hipLaunchKernelGGL( sbtPartsKernel, dim3( ( unsigned ) ( H.units / 4 ) ), dim3( 256 ), 0, ctx->stream, reinterpret_cast<const SbtPartsDev*>( base + H.offItems ),
+                      reinterpret_cast<const SbtUnit*>( base + H.offUnits ), d_resi, chroma_weight, reinterpret_cast<unsigned long long*>( d_parts ),
                       reinterpret_cast<unsigned long long*>( d_est ), d_order );
   VVHIP_LAUNCH_CHECK( ctx );
-  return sbtLaunched( ctx, S );
+  return listLaunched( ctx, S );
 }
 
 int vvhip_sbt_place_batch( vvhip_ctx* ctx, const int16_t* d_tile_rec, const vvhip_sbt_place_item* items_host, int n, const vvhip_tu_stats* d_stats, int16_t* d_rec,
@@ -470,17 +431,17 @@ int vvhip_sbt_place_batch( vvhip_ctx* ctx, const int16_t* d_tile_rec, const vvhi
     return vvhip_fail( ctx, VVHIP_E_ARG, "%s: %d items at %p, tile reconstructions %p, reconstruction %p, original residual %p (int16 arrays), SSEs %p (a uint64 array; SSEs need the original residual)",
                        entry, n, ( const void* ) items_host, ( const void* ) d_tile_rec, ( void* ) d_rec, ( const void* ) d_org_resi, ( void* ) d_sse );
   if( n == 0 ) return VVHIP_OK;
-  vvhip_ctx::IctSched& S = ctx->sbtSched[1];
+  HostList& S = ctx->list[LIST_SBT_PLACE];
   const int ptrAlign = sbtPtrAlign( { d_tile_rec, d_rec, d_sse ? d_org_resi : nullptr } );
   std::vector<unsigned char> key = sbtKey( ptrAlign, items_host, n );
   key.push_back( ( unsigned char ) ( ( d_stats ? 1 : 0 ) | ( d_tile_rec ? 2 : 0 ) ) );      // (what the validation below depends on beside the items)
   bool current = false;
-  int rc = sbtScheduleCurrent( ctx, S, key, &current );
+  int rc = listCurrent( ctx, S, key, &current );
   if( rc ) return rc;
   if( !current )
   {
     std::vector<SbtPlaceDev> dev( n );
-    std::vector<SbtKeyed> order( n );
+    std::vector<ListKeyed> order( n );
     for( int i = 0; i < n; i++ )
     {
       const vvhip_sbt_place_item& it = items_host[i];
@@ -508,11 +469,12 @@ int vvhip_sbt_place_batch( vvhip_ctx* ctx, const int16_t* d_tile_rec, const vvhi
     rc = sbtUploadSchedule( ctx, S, dev, order, []( int log2W, int log2H, int log2VY, int* log2Lanes ) { *log2Lanes = std::min( 6, log2W + log2H - log2VY ); return 64 >> *log2Lanes; }, key );
     if( rc ) return rc;
   }
-  const char* base = static_cast<const char*>( S.d_sched );
-  hipLaunchKernelGGL( sbtPlaceKernel, dim3( ( unsigned ) ( S.units / 4 ) ), dim3( 256 ), 0, ctx->stream, reinterpret_cast<const SbtPlaceDev*>( base ),
-                      reinterpret_cast<const SbtUnit*>( base + S.offUnits ), d_tile_rec, d_stats, d_rec, d_sse ? d_org_resi : nullptr, reinterpret_cast<unsigned long long*>( d_sse ) );
+  const SbtHead& H = listHead<SbtHead>( S );
+  const char* base = static_cast<const char*>( S.d );
+  hipLaunchKernelGGL( sbtPlaceKernel, dim3( ( unsigned ) ( H.units / 4 ) ), dim3( 256 ), 0, ctx->stream, reinterpret_cast<const SbtPlaceDev*>( base + H.offItems ),
+                      reinterpret_cast<const SbtUnit*>( base + H.offUnits ), d_tile_rec, d_stats, d_rec, d_sse ? d_org_resi : nullptr, reinterpret_cast<unsigned long long*>( d_sse ) );
   VVHIP_LAUNCH_CHECK( ctx );
-  return sbtLaunched( ctx, S );
+  return listLaunched( ctx, S );
 }
 
 } // extern "C"

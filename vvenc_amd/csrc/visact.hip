@@ -296,31 +296,23 @@ int vvhip_visact( vvhip_ctx* ctx, const vvhip_visact_plane* planes, int n_planes
   std::vector<VaTile> tiles;
   std::vector<VaSpan> spans;
   visactTiles( areas_host, n, tiles, spans );
-  // one blob: the tiles, then the spans
-  const size_t tileBytes = tiles.size() * sizeof( VaTile ), spanBytes = spans.size() * sizeof( VaSpan );
-  std::vector<unsigned char> blob( tileBytes + spanBytes );
-  memcpy( blob.data(), tiles.data(), tileBytes );
-  memcpy( blob.data() + tileBytes, spans.data(), spanBytes );
-  vvhip_ctx::SaoSlot& S = ctx->saoSlot[3];
-  const int rc = saoUpload( ctx, S, blob.data(), blob.size() );      // (waits for the last launches of this entry: the partial records below are free then, too)
+  // one blob: the tiles, then the spans right behind them
+  const size_t tileBytes = tiles.size() * sizeof( VaTile );
+  ListBlob blob( tiles.data(), tileBytes );
+  blob.add( spans.data(), spans.size() * sizeof( VaSpan ), 1 );
+  HostList& S = ctx->list[LIST_VISACT];
+  int rc = listUpload( ctx, S, blob );      // (waits for the last launches of this entry: the partial records below are free then, too)
   if( rc != VVHIP_OK ) return rc;
-  vvhip_ctx::SaoSlot& P = ctx->saoSlot[4];
-  const size_t partBytes = tiles.size() * 4 * sizeof( unsigned long long );
-  if( partBytes > P.bytes )
-  {
-    if( P.d ) ( void ) hipFree( P.d );
-    P.d = nullptr; P.bytes = 0;
-    const size_t want = partBytes + partBytes / 4 + 256;
-    VVHIP_CHECK_HIP( ctx, hipMalloc( &P.d, want ) );
-    P.bytes = want;
-  }
+  // the per-tile partial records: a device-only buffer in a slot of its own, guarded by the list slot's event — every launch that touches it also reads the list
+  HostList& P = ctx->list[LIST_VISACT_PART];
+  if( ( rc = listReserve( ctx, P, tiles.size() * 4 * sizeof( unsigned long long ) ) ) != VVHIP_OK ) return rc;
   A.tiles = ( const VaTile* ) S.d; A.part = ( unsigned long long* ) P.d;
   hipLaunchKernelGGL( visactTileKernel, dim3( ( unsigned ) tiles.size() ), dim3( VA_THREADS ), 0, ctx->stream, A );
   VVHIP_LAUNCH_CHECK( ctx );
   hipLaunchKernelGGL( visactSumKernel, dim3( ( unsigned ) n ), dim3( 64 ), 0, ctx->stream, ( const VaSpan* ) ( ( const unsigned char* ) S.d + tileBytes ), ( const unsigned long long* ) P.d,
                       ( unsigned long long* ) d_out );
   VVHIP_LAUNCH_CHECK( ctx );
-  return saoMark( ctx, S );
+  return listLaunched( ctx, S );
 }
 
 } // extern "C"
