@@ -1216,6 +1216,81 @@ _Static_assert( sizeof( vvhip_intra_chroma_item ) == 64, "vvhip_intra_chroma_ite
 VVHIP_API int vvhip_intra_chroma_modes_batch( vvhip_ctx* ctx, const vvhip_intra_chroma_item* items_host, int n, const int16_t* d_luma /* may be NULL */, const int16_t* d_ref,
                                               const int16_t* d_org, int16_t* d_pred /* may be NULL */, uint32_t* d_cost );
 
+/* ======================================================================================================================
+ * MMVD merge candidates of a LIST of CUs: the decision-free part of EncCu::addMmvdCandsToPruningList (EncoderLib/EncCu.cpp:2353-2453) — per CU up to 64 candidates
+ * ( MmvdIdx::ADD_NUM: two base vectors, eight steps, four directions ), each predicted (luma only) and scored with DF_HAD or DF_HAD_fast against the original, in ONE launch.
+ * Only the 64 costs of a CU leave the device: no prediction is written, and a base vector's reference window is fetched once for the candidates it can serve.
+ *   vvhip_merge_mmvd_costs_batch <- per requested candidate val = position | step << 2 | baseIdx << 5 (CommonLib/CommonDef.h:390-409), bit for bit:
+ *     1. MergeCtx::getMmvdDeltaMv (CommonLib/ContextModelling.cpp:261-342): offset = 1 << ( step + 2 ), << 2 under dis_frac (picHeader->disFracMMVD); the four directions
+ *        ( +x, -x, +y, -y ); a bi-predicted base: the copy at equal POC distances, else CU::getDistScaleFactor (CommonLib/UnitTools.cpp:1354-1371) with Mv::scaleMv
+ *        (CommonLib/Mv.h:182-187) onto the list whose reference is nearer, or the copy / mirror when either reference is long-term.
+ *     2. MergeCtx::setMmvdMergeCandiInfo (:344-404): base + delta, Mv::clipToStorageBitDepth per used list, BcwIdx only for a bi-predicted base, and
+ *        CU::restrictBiPredMergeCandsOne (UnitTools.cpp:3085-3097): a bi-predicted base on a CU with w + h == 12 is predicted from list 0 alone with the default weight.
+ *     3. InterPrediction::motionCompensation (CommonLib/InterPrediction.cpp:454-527) with mcControl = 2 | 1 (no chroma; no BDOF on an MMVD CU, :479; no DMVR: mvRefine is off):
+ *        xCheckIdenticalMotion (:292-324) — both references the same picture ( poc_delta equal ) and both stored vectors equal: list 0 alone —, then per used list clipMv
+ *        (CommonLib/Mv.cpp:68-80, applied at :382) with pic_width, pic_height, ctu_size, position = mv >> 4, fraction = mv & 15.
+ *     4. the luma prediction exactly as vvhip_pred_inter_batch_blend documents it: the 8-tap passes (m_lumaAltHpelIFilter at phase 8 under alt_hpel), one list: the clipped
+ *        sample; two lists: addAvg, or addWeightedAvg for bcw_idx != 2.
+ *     5. RdCost::xGetHADs<false> ( VVHIP_DF_HAD ) or xGetHADs<true> ( VVHIP_DF_HAD_FAST ) of original against prediction, the tile ladder of RdCost.cpp:1818-1938, as uint32.
+ *   cost width: a cost is at most that of a 128 x 128 CU at 12 bits — 256 tiles of 8 x 8, each at most 64 * 64 * 4095 / 4 (64 coefficients of at most 64 * 4095, normalised
+ *        by 4) — 256 * 4 193 280 = 1 073 479 680 < 2^32; the rectangular tiles and the 16 x 16 fast tile ( an 8 x 8 transform of averages, times 4 ) stay below the same figure.
+ * Planes: the table of vvhip_pred_inter_batch (<= 16 planes, stride > 0 and even).  ref_off[b][l] is the CU's own position (vector zero) in plane ref_plane[b][l].
+ * Original: d_org + org_off, row pitch org_stride.  Costs: d_cost + cost_off addresses 64 uint32 slots indexed by val; the slots of cand_mask ( bit val & 31 of word val >> 5 )
+ * are written, the others are not touched.
+ * An item's results depend on nothing but the item: independent of the list's order and identical from run to run (integer arithmetic; a CU larger than a tile of 512 samples
+ * is cut into tiles whose partial sums are added as integers).  items_host is a HOST array, validated and uploaded by the call.  n == 0 succeeds and launches nothing.
+ * Read bound: after the picture clip a block reads at most ctu_size + 8 + 3 samples left of / above the picture and at most 8 + w + 4 ( 8 + h + 4 ) samples right of / below
+ * it — with CUs no larger than the CTU inside the reference encoder's own picture margin of ctu_size + 16 —, plus the 16 bytes of the aligned-dword rule.  The window the kernel stages around
+ * a base vector's own (clipped) position is moved back into the same region, so it adds nothing to the bound.  Every plane of the table must be readable that far.
+ * VVHIP_E_ARG with a message naming the entry, before any launch and with nothing written: n < 0; w or h not a power of two in 4..128, or w + h < 12; bit_depth outside 8..12;
+ * func other than VVHIP_DF_HAD / VVHIP_DF_HAD_FAST; a base with both lists unused while one of its candidates is requested; a plane index outside the table; bcw_idx > 4;
+ * ctu_size other than 32, 64, 128; a CU outside the picture; a negative org_off, cost_off or ref_off of a used list; a base vector outside the 18-bit storage range;
+ * non-zero reserved bytes; planes / items / d_org / d_cost missing with n > 0.
+ * Still the caller's: the merge list itself (getInterMergeCandidates, getInterMMVDMergeCandidates), xCalcPuMeBits and lambda; insertMergeItemToList and shrinkList, and the
+ * visiting order of addMmvdCandsToPruningList / xCheckMMVDCand (EncCu.cpp:2361-2447, :4116-4158), which runs unchanged over ready costs ( vvhip::MergeMmvdOps::walk of the shim restates it for a caller that wants the order without the loop ); the isMvInRangeFPP skip under m_ifpLines; the candidates the
+ * reference's SATD stage predicts WITH BDOF ( m_MMVD == 1 and step <= 2 under the conditions of InterPrediction.cpp:474-479: leave them out of the mask and take them through
+ * vvhip_pred_inter_batch_ex ); regular, CIIP, affine and GPM candidates; chroma; explicit weighted prediction and reference picture resampling; the survivors' predictions
+ * (vvhip_mmvd_candidate gives what vvhip_pred_inter_batch_blend needs); hooking the entry into the running encoder.
+ * Bit depths 8..12.  Differences are scored at 32 bits.                                                                                                                         */
+typedef struct
+{
+  int16_t  cu_x, cu_y;             /* the CU's luma position in the picture                                        */
+  uint8_t  w, h;                   /* powers of two 4..128, w + h >= 12                                            */
+  uint8_t  rsv0[2];                /* 0                                                                            */
+  int32_t  org_off;                /* into d_org                                                                   */
+  int32_t  cost_off;               /* into d_cost: 64 slots indexed by MmvdIdx::val                                */
+  uint32_t cand_mask[2];           /* word b: the candidates of base vector b, bit position | step << 2            */
+  int32_t  mv[2][2][2];            /* [base][list]( hor, ver ) in 1/16 sample: mmvdBaseMv[b][l].mv                 */
+  int32_t  ref_off[2][2];          /* [base][list] the CU at vector zero in plane ref_plane[b][l]                  */
+  int32_t  poc_delta[2][2];        /* [base][list] POC of the reference picture minus the current POC              */
+  int8_t   ref_plane[2][2];        /* [base][list] index into the plane table, -1 = list not used                  */
+  uint8_t  long_term[2];           /* per base: bit l = list l's reference is a long-term picture                  */
+  uint8_t  bcw_idx[2];             /* per base: BcwIdx[b], 0..4 (applies when both lists are used)                 */
+  uint8_t  alt_hpel[2];            /* per base: mmvdUseAltHpelIf[b]                                                */
+  uint8_t  rsv[14];                /* 0                                                                            */
+} vvhip_mmvd_item;                 /* 112 bytes */
+#ifdef __cplusplus
+static_assert( sizeof( vvhip_mmvd_item ) == 112, "vvhip_mmvd_item is 112 bytes" );
+#else
+_Static_assert( sizeof( vvhip_mmvd_item ) == 112, "vvhip_mmvd_item is 112 bytes" );
+#endif
+VVHIP_API int vvhip_merge_mmvd_costs_batch( vvhip_ctx* ctx, const vvhip_me_plane* planes_host, int n_planes, const vvhip_mmvd_item* items_host, int n,
+                                            int pic_width, int pic_height, int ctu_size /* luma: 32, 64, 128 */, int bit_depth, int func, int dis_frac,
+                                            const int16_t* d_org, int org_stride, uint32_t* d_cost );
+/* One candidate of an item as the entry above predicts it, on the host (no device, no context): steps 1 to 3.  stored_mv is cu.mv after setMmvdMergeCandiInfo (the storage
+ * clip, ( 0, 0 ) for an unused list); mv the vector after the picture clip, from which a vvhip_pred_item takes ref_off[b][l] + ( mv >> 4 ) and frac = mv & 15; ref_plane -1
+ * for a list the prediction does not use (the base's own, bi-to-uni at w + h == 12, identical motion); bcw_idx 2 unless two lists are predicted; alt_hpel the base's.
+ * Returns VVHIP_E_ARG for val outside 0..63, a base with both lists unused, a size outside the rule or a ctu_size outside the set.                                            */
+typedef struct
+{
+  int32_t  mv[2][2];               /* per list ( hor, ver ) after clipMv                                           */
+  int32_t  stored_mv[2][2];        /* per list ( hor, ver ) as cu.mv holds it                                      */
+  int8_t   ref_plane[2];           /* -1: the list is not predicted                                                */
+  uint8_t  bcw_idx;                /* 0..4                                                                         */
+  uint8_t  alt_hpel;
+} vvhip_mmvd_cand;                 /* 36 bytes */
+VVHIP_API int vvhip_mmvd_candidate( const vvhip_mmvd_item* item, int val, int pic_width, int pic_height, int ctu_size, int dis_frac, vvhip_mmvd_cand* out );
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ enum ListSlot
   LIST_DEBLOCK,                                    // deblock.hip, per call: the band's loop-filter records of vvhip_deblock
   LIST_VISACT, LIST_VISACT_PART,                   // visact.hip, per call: the tile list and area table of vvhip_visact; its per-tile partial records (device only, see there)
   LIST_INTRA, LIST_INTRA_CHROMA,                   // intra.hip, intrachroma.hip, per call: the items of vvhip_intra_luma_modes_batch, of vvhip_intra_chroma_modes_batch
+  LIST_MMVD,                                       // mmvd.hip, per call: the items and tiles of vvhip_merge_mmvd_costs_batch
   LIST_COUNT
 };
 

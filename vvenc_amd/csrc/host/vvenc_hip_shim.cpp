@@ -1942,6 +1942,181 @@ void IntraChromaOps::select( const uint32_t cost[8], const uint8_t cand[8], bool
 
 IntraChromaOps::~IntraChromaOps() {}      // (device areas are released with the process, like ALFOps')
 
+// ------------------------------------------------------------------------------------------------ MergeMmvdOps
+void MergeMmvdOps::begin( int picWidth, int picHeight, int ctuSize, int bitDepth, int curPoc, bool disFracMMVD, bool hadFast, const Pel* orgPlane )
+{
+  m_items.clear(); m_planes.clear(); m_cost.clear(); m_ran = false;
+  m_picW = picWidth; m_picH = picHeight; m_ctu = ctuSize; m_bitDepth = bitDepth; m_curPoc = curPoc; m_disFrac = disFracMMVD;
+  m_func = hadFast ? VVHIP_DF_HAD_FAST : VVHIP_DF_HAD; m_org = orgPlane;
+}
+
+int MergeMmvdOps::add( int cuX, int cuY, int width, int height, const Base base[2], uint64_t mask )
+{
+  auto sizeOk = []( int v ) { return v >= 4 && v <= 128 && !( v & ( v - 1 ) ); };
+  if( !base || !m_org || !sizeOk( width ) || !sizeOk( height ) || width + height < 12 || m_bitDepth < 8 || m_bitDepth > 12 || ( m_ctu != 32 && m_ctu != 64 && m_ctu != 128 ) ||
+      cuX < 0 || cuY < 0 || cuX + width > m_picW || cuY + height > m_picH ) return -1;
+  vvhip_mmvd_item q;
+  memset( &q, 0, sizeof( q ) );
+  q.cu_x = ( int16_t ) cuX; q.cu_y = ( int16_t ) cuY; q.w = ( uint8_t ) width; q.h = ( uint8_t ) height;
+  q.cand_mask[0] = ( uint32_t ) mask; q.cand_mask[1] = ( uint32_t ) ( mask >> 32 );
+  q.cost_off = ( int32_t ) ( 64 * m_items.size() );
+  std::vector<const Pel*> planes = m_planes;                         // (the table grows only when the CU is accepted)
+  for( int b = 0; b < 2; b++ )
+  {
+    const Base& s = base[b];
+    if( !s.refPlane[0] && !s.refPlane[1] && q.cand_mask[b] ) return -1;
+    if( s.bcwIdx < 0 || s.bcwIdx > 4 ) return -1;
+    q.bcw_idx[b] = ( uint8_t ) s.bcwIdx; q.alt_hpel[b] = s.altHpel ? 1 : 0;
+    for( int l = 0; l < 2; l++ )
+    {
+      q.ref_plane[b][l] = -1;
+      if( !s.refPlane[l] ) continue;
+      if( s.mvHor[l] < -( 1 << 17 ) || s.mvHor[l] >= ( 1 << 17 ) || s.mvVer[l] < -( 1 << 17 ) || s.mvVer[l] >= ( 1 << 17 ) ) return -1;
+      size_t k = std::find( planes.begin(), planes.end(), s.refPlane[l] ) - planes.begin();
+      if( k == planes.size() ) { if( k == 16 ) return -1; planes.push_back( s.refPlane[l] ); }
+      q.ref_plane[b][l] = ( int8_t ) k;
+      q.mv[b][l][0] = s.mvHor[l]; q.mv[b][l][1] = s.mvVer[l];
+      q.poc_delta[b][l] = s.refPoc[l] - m_curPoc;
+      q.long_term[b] = ( uint8_t ) ( q.long_term[b] | ( s.longTerm[l] ? 1 << l : 0 ) );
+    }
+  }
+  m_planes.swap( planes );
+  m_items.push_back( q );
+  m_ran = false;
+  return ( int ) m_items.size() - 1;
+}
+
+bool MergeMmvdOps::run()
+{
+  if( m_items.empty() ) return false;
+  Device& dev = Device::get();
+  auto mirrorOf = [&dev]( const Pel* p ) { Device::Found f = dev.findReference( p ); return f ? f : dev.find( p ); };
+  vvhip_me_plane table[16];
+  for( size_t k = 0; k < m_planes.size(); k++ )
+  {
+    const Device::Found f = mirrorOf( m_planes[k] );
+    if( !f ) return false;
+    table[k].d_base = f->dOrigin + ( m_planes[k] - f->origin ); table[k].stride = f->stride; table[k].reserved = 0;
+  }
+  const Device::Found fo = mirrorOf( m_org );
+  if( !fo ) return false;
+  const int16_t* dOrg = fo->dOrigin + ( m_org - fo->origin );
+  // the CU at vector zero, at each plane's own line pitch
+  for( vvhip_mmvd_item& q : m_items )
+  {
+    q.org_off = ( int32_t ) ( ( ptrdiff_t ) q.cu_y * fo->stride + q.cu_x );
+    for( int b = 0; b < 2; b++ )
+      for( int l = 0; l < 2; l++ )
+        if( q.ref_plane[b][l] >= 0 ) q.ref_off[b][l] = ( int32_t ) ( ( ptrdiff_t ) q.cu_y * table[q.ref_plane[b][l]].stride + q.cu_x );
+  }
+  const size_t total = ( m_items.size() * 64 * sizeof( uint32_t ) + 255 ) & ~( size_t ) 255;
+  if( m_gpu != dev.gpu() || m_devBytes < total )
+  {
+    if( m_d && m_gpu == dev.gpu() ) vvhip_free( dev.ctx(), m_d );      // (an area of another GPU is released with the process)
+    void* p = nullptr;
+    m_d = nullptr; m_devBytes = 0;
+    dev.check( vvhip_malloc( dev.ctx(), &p, total ), "MMVD cost list" );
+    m_d = static_cast<char*>( p ); m_devBytes = total; m_gpu = dev.gpu();
+  }
+  uint32_t* dCost = reinterpret_cast<uint32_t*>( m_d );
+  dev.check( vvhip_merge_mmvd_costs_batch( dev.ctx(), table, ( int ) m_planes.size(), m_items.data(), ( int ) m_items.size(), m_picW, m_picH, m_ctu, m_bitDepth, m_func, m_disFrac ? 1 : 0,
+                                           dOrg, fo->stride, dCost ), "vvhip_merge_mmvd_costs_batch" );
+  m_cost.assign( m_items.size() * 64, 0 );
+  dev.check( vvhip_download( dev.ctx(), m_cost.data(), dCost, m_cost.size() * sizeof( uint32_t ) ), "MMVD costs" );
+  // slots that were not scored hold whatever the device area held: they read 0
+  for( size_t i = 0; i < m_items.size(); i++ )
+    for( int v = 0; v < 64; v++ ) if( !scored( ( int ) i, v ) ) m_cost[64 * i + v] = 0;
+  m_ran = true;
+  return true;
+}
+
+uint64_t MergeMmvdOps::bdofCands( int width, int height, const Base base[2], int curPoc, int mmvd, bool bdofEnabled, bool bcwEnabled )
+{
+  uint64_t out = 0;
+  if( !bdofEnabled || mmvd != 1 ) return 0;
+  for( int b = 0; b < 2; b++ )
+  {
+    const Base& s = base[b];
+    const bool bi = s.refPlane[0] && s.refPlane[1] && width + height != 12;                          // restrictBiPredMergeCandsOne cuts the others to list 0
+    if( !bi || s.longTerm[0] || s.longTerm[1] || curPoc - s.refPoc[0] != s.refPoc[1] - curPoc ) continue;
+    if( std::min( width, height ) < 8 || width * height < 128 || ( bcwEnabled && s.bcwIdx != 2 ) ) continue;
+    out |= ( uint64_t ) 0xfff << ( 32 * b );                                                      // steps 0, 1, 2 in their four directions
+  }
+  return out;
+}
+
+int MergeMmvdOps::walk( const uint32_t dist[64], const double bitsCost[64], const double* listCost, int nList, const WalkCfg& cfg, uint8_t tested[64], double* bestCostOffsetOut,
+                        double* bestCostMergeOut, int* bestDirOut )
+{
+  const int    refineNum = 32;                                        // MMVD_MAX_REFINE_NUM
+  const double maxDouble = 1.7e+308;                                  // MAX_DOUBLE
+  std::vector<double> list( listCost, listCost + std::max( nList, 0 ) );
+  const size_t curListSize = list.size();
+  int n = 0;
+  if( curListSize == 0 ) return 0;
+  int    mmvdTestNum    = cfg.numValidMergeCand > 1 ? 64 : 32;
+  int    bestDir        = 0;
+  double bestCostMerge  = list[curListSize - 1];
+  double bestCostOffset = maxDouble;
+  int    shiftCandStart = 0;
+  if( cfg.mmvd == 4 )
+  {
+    if( cfg.mrgCnd0 > 1 && cfg.mrgCnd1 > 1 ) mmvdTestNum = 0;
+    else if( cfg.mrgCnd0 > 1 || cfg.mrgCnd1 > 1 )
+    {
+      const int shiftCand = cfg.mrgCnd0 < 2 ? cfg.mrgCnd0 : cfg.mrgCnd1;
+      if( shiftCand ) shiftCandStart = refineNum; else mmvdTestNum = refineNum;
+    }
+  }
+  for( int cand = shiftCandStart; cand < mmvdTestNum; cand++ )
+  {
+    int val = cand;
+    if( ( ( val >> 2 ) & 7 ) >= cfg.mmvdDisNum ) continue;
+    if( cfg.mmvd > 1 )
+    {
+      // xCheckMMVDCand
+      int check = 0;
+      const int candCur = val & ( refineNum - 1 );
+      bool stop = false;
+      if( cfg.mmvd > 2 && candCur % 4 == 0 )
+      {
+        if( bestCostOffset >= bestCostMerge && candCur >= 4 )
+        {
+          if( val > refineNum ) stop = true;
+          else { val = refineNum; if( mmvdTestNum == val ) stop = true; }
+        }
+        if( !stop ) { bestCostOffset = maxDouble; bestCostMerge = list[curListSize - 1]; }
+      }
+      if( stop ) break;
+      if( val == refineNum ) bestDir = 0;
+      if( candCur >= 4 && candCur % 4 != bestDir ) check = 1;          // ( candCur is the value on entry, as in the reference )
+      cand = val;
+      if( check ) continue;
+    }
+    if( ( cfg.skip >> val ) & 1 ) continue;
+    const double cost = ( double ) dist[val] + bitsCost[val];
+    tested[n++] = ( uint8_t ) val;
+    // insertMergeItemToList on the costs
+    if( cfg.maxTrackingNum > 0 && ( int ) list.size() == cfg.maxTrackingNum && cost >= list.back() ) {}
+    else
+    {
+      if( cfg.maxTrackingNum > 0 && ( int ) list.size() == cfg.maxTrackingNum ) list.pop_back();
+      list.insert( std::find_if( list.begin(), list.end(), [cost]( double c ) { return cost < c; } ), cost );
+    }
+    if( cfg.mmvd > 1 && cost < bestCostOffset )
+    {
+      bestCostOffset = cost;
+      if( ( val & ( refineNum - 1 ) ) < 4 ) bestDir = val & ( refineNum - 1 );
+    }
+  }
+  if( bestCostOffsetOut ) *bestCostOffsetOut = bestCostOffset;
+  if( bestCostMergeOut ) *bestCostMergeOut = bestCostMerge;
+  if( bestDirOut ) *bestDirOut = bestDir;
+  return n;
+}
+
+MergeMmvdOps::~MergeMmvdOps() {}      // (device areas are released with the process, like ALFOps')
+
 bool ALFOps::getStatisticsCcAlf( const Pel* orgC, int orgStride, const Pel* slfC, int slfStride, const Pel* recLuma, int recStride, int widthC, int heightC, int ctuSizeC,
                                  int vbCTUHeight, int vbPos, int picHeight, float* out, const float* init )
 {

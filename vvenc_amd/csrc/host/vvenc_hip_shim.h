@@ -546,6 +546,67 @@ private:
   std::vector<uint32_t> m_cost;
 };
 
+// MMVD merge candidates (vvhip_merge_mmvd_costs_batch): the predict-and-score part of EncCu::addMmvdCandsToPruningList (EncoderLib/EncCu.cpp:2353-2453) for a list of CUs —
+// per CU and requested candidate MergeCtx::setMmvdMergeCandiInfo, the luma prediction of motionCompensation with mcControl = 2 | 1 and DF_HAD / DF_HAD_fast against the
+// original.  The merge list, xCalcPuMeBits, lambda, insertMergeItemToList / shrinkList, the isMvInRangeFPP skip and the candidates predicted WITH BDOF stay with the encoder;
+// walk() restates the visiting order for it over ready costs and bdofCands() names the candidates to leave out of the mask.
+struct MergeMmvdOps
+{
+  // one base vector as MergeCtx holds it (CommonLib/ContextModelling.h:521-533): mmvdBaseMv[b][l].mv, the reference picture behind mmvdBaseMv[b][l].refIdx — refPlane[l] is the
+  // host pointer to luma sample ( 0, 0 ) of a picture registered with Device::registerPicture (nullptr: list l unused), refPoc[l] its POC, longTerm[l] its isLongTerm —,
+  // BcwIdx[b] and mmvdUseAltHpelIf[b]
+  struct Base { int mvHor[2] = { 0, 0 }, mvVer[2] = { 0, 0 }; const Pel* refPlane[2] = { nullptr, nullptr }; int refPoc[2] = { 0, 0 }; bool longTerm[2] = { false, false }; int bcwIdx = 2; bool altHpel = false; };
+  // begin empties the list and fixes what one call fixes: the picture's luma size and CTU size (the picture clip), the bit depth, the current POC, picHeader->disFracMMVD,
+  // hadFast ( true: DF_HAD_fast, false: DF_HAD — the two values EncCu.cpp:1961 chooses from ) and orgPlane, the host pointer to luma sample ( 0, 0 ) of the original picture
+  // (registered like the references).
+  // add appends one CU at luma position ( cuX, cuY ) with its two base vectors and the candidates to score (bit MmvdIdx::val of mask).  -> the CU's index, -1 for what the entry
+  // would refuse on sight (size, position, bcwIdx, a requested candidate of a base without lists, a vector outside the storage range) or a 17th distinct reference plane.
+  // run resolves the planes' mirrors, runs the entry on the calling thread's stream and downloads the costs; false: an empty list, or a plane that is not registered on this
+  // GPU (nothing was run).
+  void begin( int picWidth, int picHeight, int ctuSize, int bitDepth, int curPoc, bool disFracMMVD, bool hadFast, const Pel* orgPlane );
+  int  add( int cuX, int cuY, int width, int height, const Base base[2], uint64_t mask );
+  bool run();
+  int  count() const { return ( int ) m_items.size(); }
+  bool scored( int i, int val ) const { return val >= 0 && val < 64 && ( ( m_items.at( i ).cand_mask[val >> 5] >> ( val & 31 ) ) & 1 ); }
+  uint32_t dist( int i, int val ) const { return m_cost.at( ( size_t ) 64 * i + val ); }      // the Hadamard sum of a scored candidate (Distortion); 0 where it was not scored
+  const uint32_t* dists( int i ) const { return &m_cost.at( ( size_t ) 64 * i ); }            // the CU's 64 slots, indexed by MmvdIdx::val
+
+  // The candidates of a CU that the reference's SATD stage predicts WITH BDOF — to be left out of the mask and taken through vvhip_pred_inter_batch_ex: none unless
+  // sps->BDOF && !picHeader->disBdofFlag ( bdofEnabled ) and m_MMVD == 1; then, per base, the steps 0 .. 2 ( mccNoBdof is off for them, EncCu.cpp:2225 ) where
+  // InterPrediction.cpp:474-479 holds: both lists used and not cut to one ( width + height != 12 ), neither reference long-term, curPoc - refPoc[0] == refPoc[1] - curPoc,
+  // min( width, height ) >= 8, width * height >= 128 and ( !sps->BCW ( bcwEnabled ) || bcwIdx == 2 ).  Host arithmetic only.
+  static uint64_t bdofCands( int width, int height, const Base base[2], int curPoc, int mmvd, bool bdofEnabled, bool bcwEnabled );
+
+  // The visiting order of addMmvdCandsToPruningList with xCheckMMVDCand (EncCu.cpp:2361-2447, :4116-4158) over costs that are already there.  Host arithmetic only.
+  struct WalkCfg
+  {
+    int mmvd = 3;                       // m_MMVD, 1 .. 4
+    int mmvdDisNum = 6;                 // m_MmvdDisNum
+    int numValidMergeCand = 2;          // mergeCtx.numValidMergeCand: one base vector only when it is 1
+    int mrgCnd0 = 0, mrgCnd1 = 1;       // m_MMVD == 4: mergeIdx of the incoming list's entry 0 and of its entry 1 ( of entry 0 again when the list holds one item )
+    int maxTrackingNum = 0;             // the list's m_maxTrackingNum (EncCu.cpp:4444-4471); <= 0: the list may grow without bound
+    uint64_t skip = 0;                  // candidates the caller's isMvInRangeFPP test drops (m_ifpLines): visited by xCheckMMVDCand, neither tested nor counted
+  };
+  // dist[64]: the candidates' distortions; bitsCost[64]: the caller's fracBits * lambda per candidate, so that a candidate's cost is ( double ) dist + bitsCost as
+  // calcLumaCost4MergePrediction forms it; listCost[ nList ], nList >= 1: the costs of the incoming m_mergeItemList in its own (ascending) order — the reference re-reads entry
+  // nList - 1 of the list after every insertion, so the walk inserts each tested candidate's cost as insertMergeItemToList does.  tested[64] receives the MmvdIdx::val of
+  // the candidates the reference would have predicted and scored, in order -> their number.  bestCostOffset / bestCostMerge / bestDir (may be NULL) receive the three
+  // running values as the loop leaves them.
+  static int walk( const uint32_t dist[64], const double bitsCost[64], const double* listCost, int nList, const WalkCfg& cfg, uint8_t tested[64],
+                   double* bestCostOffset = nullptr, double* bestCostMerge = nullptr, int* bestDir = nullptr );
+  ~MergeMmvdOps();
+private:
+  bool m_ran = false;
+  int m_gpu = -1, m_picW = 0, m_picH = 0, m_ctu = 0, m_bitDepth = 0, m_curPoc = 0, m_func = 0;
+  bool m_disFrac = false;
+  const Pel* m_org = nullptr;
+  size_t m_devBytes = 0;
+  char* m_d = nullptr;
+  std::vector<const Pel*> m_planes;
+  std::vector<vvhip_mmvd_item> m_items;
+  std::vector<uint32_t> m_cost;
+};
+
 // MCTF table, CommonLib/MCTF.h:160-170
 struct MCTFOps
 {

@@ -118,6 +118,11 @@ INTRA_CHROMA_ITEM_DTYPE = np.dtype([("w", "u1"), ("h", "u1"), ("bit_depth", "u1"
                                     ("pred_off", "<i4", 2), ("cost_off", "<i4"), ("rsv", "u1", 12)])      # vvhip_intra_chroma_item (64 bytes)
 INTRA_CHROMA_SLOTS = 8      # NUM_CHROMA_MODE: the candidate and cost slots of an item
 ICH_ABOVE, ICH_LEFT, ICH_FIRST_ROW, ICH_VER_COLLOCATED = 1, 2, 4, 8
+MMVD_ITEM_DTYPE = np.dtype([("cu_x", "<i2"), ("cu_y", "<i2"), ("w", "u1"), ("h", "u1"), ("rsv0", "u1", 2), ("org_off", "<i4"), ("cost_off", "<i4"), ("cand_mask", "<u4", 2),
+                            ("mv", "<i4", (2, 2, 2)), ("ref_off", "<i4", (2, 2)), ("poc_delta", "<i4", (2, 2)), ("ref_plane", "i1", (2, 2)), ("long_term", "u1", 2),
+                            ("bcw_idx", "u1", 2), ("alt_hpel", "u1", 2), ("rsv", "u1", 14)])      # vvhip_mmvd_item (112 bytes)
+MMVD_CAND_DTYPE = np.dtype([("mv", "<i4", (2, 2)), ("stored_mv", "<i4", (2, 2)), ("ref_plane", "i1", 2), ("bcw_idx", "u1"), ("alt_hpel", "u1")])      # vvhip_mmvd_cand (36 bytes)
+MMVD_SLOTS = 64      # MmvdIdx::ADD_NUM: the cost slots of an item, indexed by position | step << 2 | baseIdx << 5
 SBT_MAX_DIST = (1 << 64) - 1      # MAX_DISTORTION: the estimate of a mode whose type is not allowed
 
 
@@ -929,6 +934,33 @@ class HotPath:
         assert cost.dtype == torch.int32 and ref.dtype == torch.int16 and org.dtype == torch.int16 and (pred is None or pred.dtype == torch.int16) and (luma is None or luma.dtype == torch.int16)
         self._ck(self.L.vvhip_intra_chroma_modes_batch(self.ctx, it.ctypes.data_as(C.c_void_p), it.size, _ptr(luma), _ptr(ref), _ptr(org), _ptr(pred), _ptr(cost)))
         return cost, pred, it
+
+    # ---- MMVD merge candidates (mmvd.hip) ----
+    def merge_mmvd_costs(self, planes, items, org, pic_w, pic_h, ctu, bit_depth=10, func="HAD", dis_frac=False, cost=None):
+        """vvhip_merge_mmvd_costs_batch: the Hadamard cost of every candidate of cand_mask of every CU of the list — base vector plus MMVD delta, the clips, the luma
+        prediction (one list, the default average or BCW) and HAD / HAD_fast against the original, in one launch.  planes: the reference Planes the items' ref_plane
+        indexes; items: MMVD_ITEM_DTYPE [ n ] (HOST array); org: the Plane of the original.  Without cost the items get cost_off = 64 * i and a fresh zeroed tensor is
+        returned; with cost ( int32, the uint32 costs ) the items' own cost_off is used and nothing but the requested slots is written.
+        -> ( cost viewed as ( -1, 64 ) where it was made here, the items as run )"""
+        it = np.ascontiguousarray(items, MMVD_ITEM_DTYPE).reshape(-1)
+        if cost is None:
+            it = it.copy()
+            it["cost_off"] = MMVD_SLOTS * np.arange(it.size)
+            cost = torch.zeros((it.size, MMVD_SLOTS), dtype=torch.int32, device=self.device)
+        assert cost.dtype == torch.int32
+        tab = (self._MePlane * max(1, len(planes)))(*[self._MePlane(p.buf_ptr.value, p.stride, 0) for p in planes])
+        self._ck(self.L.vvhip_merge_mmvd_costs_batch(self.ctx, C.cast(tab, C.c_void_p), len(planes), it.ctypes.data_as(C.c_void_p) if it.size else None, int(it.size),
+                                                     int(pic_w), int(pic_h), int(ctu), bit_depth, DF[func] if isinstance(func, str) else func, int(dis_frac),
+                                                     org.buf_ptr if org is not None else None, org.stride if org is not None else 0, _ptr(cost)))
+        return cost, it
+
+    def mmvd_candidate(self, item, val, pic_w, pic_h, ctu, dis_frac=False):
+        """vvhip_mmvd_candidate (host only): candidate val of one MMVD_ITEM_DTYPE record -> a MMVD_CAND_DTYPE record"""
+        it = np.ascontiguousarray(item, MMVD_ITEM_DTYPE).reshape(-1)[:1].copy()
+        out = np.zeros(1, MMVD_CAND_DTYPE)
+        if self.L.vvhip_mmvd_candidate(it.ctypes.data_as(C.c_void_p), int(val), int(pic_w), int(pic_h), int(ctu), int(dis_frac), out.ctypes.data_as(C.c_void_p)) != 0:
+            raise ValueError("mmvd_candidate: candidate %d of a %dx%d item" % (val, int(it[0]["w"]), int(it[0]["h"])))
+        return out[0]
 
     # ---- SURVEY 8f rank 2: MCTF apply side ----
     REF_STRENGTHS = ((0.84375, 0.6, 0.4286, 0.3333, 0.2727, 0.2308), (1.12500, 1.0, 0.7143, 0.5556, 0.4545, 0.3846))      # MCTF.cpp:112-117

@@ -128,6 +128,8 @@ PROTOTYPES = {
     "vvhip_visact": (i32, [vp, vp, i32, vp, i32, vp]),
     "vvhip_intra_luma_modes_batch": (i32, [vp, vp, i32, vp, vp, vp, vp]),
     "vvhip_intra_chroma_modes_batch": (i32, [vp, vp, i32, vp, vp, vp, vp, vp]),
+    "vvhip_merge_mmvd_costs_batch": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
+    "vvhip_mmvd_candidate": (i32, [vp, i32, i32, i32, i32, i32, vp]),
     "vvhip_mctf_set_stats": (i32, [vp, i32]),
     "vvhip_mctf_get_stats": (i32, [vp, vp]),
     "vvhip_mctf_set_timing": (i32, [vp, i32]),
