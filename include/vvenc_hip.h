@@ -496,7 +496,9 @@ VVHIP_API int vvhip_subpel_refine_batch( vvhip_ctx* ctx, int func, const int16_t
  *   masked item  : DF_SAD_WITH_MASK (xGetSADwMask, RdCost.cpp:2062-2093: GEO partitions of preset medium and slower): sum |org - cur| * mask over the rows the
  *                  subShift rule keeps, << subShift.  The mask block is COMPACT (row pitch = width, one row per evaluated row: the caller has applied the
  *                  reference's stepX / maskStride / maskStride2 walk).  Its costs follow the plain items': d_item_cost[n_items + i].
- * Offsets are in samples from sample (0,0) of the job's plane (negative = margin); planes must be readable 16 bytes beyond every block / window row they hold.
+ * Offsets are in samples from sample (0,0) of the job's plane (negative = margin); planes must be readable 16 bytes beyond every block row they hold, and 18 bytes beyond
+ * every row of an integer job's window (the candidates' bounding box + the block: a row of winW samples is fetched as ( winW + 2 + 7 ) / 8 chunks of 16 bytes from its
+ * first sample, i.e. up to 9 samples further when winW = 7 mod 8).
  * A plane table entry with stride 0 is a pool of COMPACT blocks: the row pitch of a block read from it is the block's own width.
  * Shapes (round 4: everything preset medium's CTU 128 + multi-type tree produces): width and height independent powers of two — integer jobs 8..128 x 4..128,
  * stage jobs 4..128 x 4..128 (not 4x4), items 2..128 x 2..128; the Hadamard family follows the reference's tile ladder (16x8, 8x16, 8x4, 4x8 with the
@@ -504,6 +506,9 @@ VVHIP_API int vvhip_subpel_refine_batch( vvhip_ctx* ctx, int func, const int16_t
  * Operand ranges of the Hadamard family (stage jobs and items): what the encoder hands to these table entries at the plan's bit depth — samples in [0, 2^bit_depth) or
  * bi-prediction patterns 2 org - pred in (-2^bit_depth, 2^(bit_depth+1)) against prediction samples, i.e. |org - cur| < 2^(bit_depth+1): the first two butterfly stages run on
  * packed 16-bit pairs.  SAD / SSE / masked-SAD items take any int16 operands (masked SADs: weights >= 0; sums in 64 bits outside the GEO range of samples and weights).
+ * Operand range of integer jobs: ANY int16 values in both planes, -32768 .. 32767 (samples, bi-prediction patterns and beyond).  The window kernel flips the sign bit of
+ * both operands ( x ^ 0x8000 = x + 32768 as uint16: order and differences are kept ), v_sad_u16 adds |a - b| of the unsigned halves into a 32-bit sum per lane, the team's
+ * sums are added in 32 bits and shifted by sub_shift in 64: exact up to 128 * 128 * 65535 < 2^32 (tests/test_gpu_me_plan_extremes.py, family F, at both ends of the range).
  * Limits: fewer than 2^24 candidates and 2^22 stage jobs per plan.
  * Integer jobs: positions a job lists more than once (the search re-scores its start point) are scored once; every listed candidate still gets its cost.
  * A plan owns device copies of the job tables and the schedule derived from them (which wave takes which jobs, heaviest first); running it is one launch per kind.

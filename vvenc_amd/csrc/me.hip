@@ -22,7 +22,10 @@
 // precomputed by plan creation, a cap on the serial work of one workgroup (candidates per window, row groups per bundle, units per wave), and — round 4 — every launch's
 // workgroups in XCD-band order (xcdBandOrder): each XCD's private L2 streams one horizontal band of the picture.
 // Results are bit-exact with the reference's table entries (tests: the CPU restatement directly over every shape, tests/test_gpu_me_shapes.py; the recorded costs of the real encoder,
-// tests/test_gpu_replay.py; the per-function kernels of dist.hip / interp.hip).
+// tests/test_gpu_replay.py; the per-function kernels of dist.hip / interp.hip; the deterministic limits of the scheduler and of the kernels' address arithmetic — window extents at
+// the reach, candidate caps and repeats at the team size, the three LDS classes and their launches, every stage position, deal and bundle limit, item runs at the wave size and
+// beyond 65 536 waves, int16 operands of the windows, vvhip_me_plan_run_parts, the VVHIP_ME_* knobs — tests/test_gpu_me_plan_extremes.py on the cases of
+// tests/me_plan_extremes.py, whose schedule_model restates the counting rules of mePlanCreate below: a change of the schedule changes that function too).
 #include <stdlib.h>
 #ifndef VVHIP_ME_HU
 #define VVHIP_ME_HU 2

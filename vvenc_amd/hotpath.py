@@ -716,6 +716,10 @@ class HotPath:
     def me_plan_run(self, plan, plane_table, n_planes, cand_cost, stage_cost, item_cost):
         self._ck(self.L.vvhip_me_plan_run(self.ctx, plan, C.cast(plane_table, C.c_void_p), n_planes, _ptr(cand_cost), _ptr(stage_cost), _ptr(item_cost)))
 
+    def me_plan_run_parts(self, plan, plane_table, n_planes, cand_cost, stage_cost, item_cost, parts):
+        """parts: bit 0 refinement stages, bit 1 integer windows, bit 2 table calls — only the cost arrays of the parts that run are written"""
+        self._ck(self.L.vvhip_me_plan_run_parts(self.ctx, plan, C.cast(plane_table, C.c_void_p), n_planes, _ptr(cand_cost), _ptr(stage_cost), _ptr(item_cost), int(parts)))
+
     # ---- SURVEY 8f rank 3: DMVR refinement search ----
     def dmvr_refine_batch(self, ref0, ref1, d_items, n, dx, dy, bit_depth=10, out=None):
         """d_items: DMVR_ITEM_DTYPE records -> tensor of DMVR_RESULT_DTYPE records (as uint8 rows)"""
